@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[1], the configuration the metric is quoted on):
 `sym_solve` on 1e8 random 4x4 SPD compact-sym fp32 systems per GPU (AoS layout, the
@@ -21,13 +21,21 @@ max-over-ranks of the wall time and a census of the ranks/devices (`ranks_seen`,
 Prints ONE JSON line (rank 0) with the contract fields plus
   "roofline":     HBM roofline of the dominant kernel: algorithmic bytes per launch /
                   launch duration (HIP events on the launch stream, one per step: mean,
-                  median and min are reported; `achieved` uses the mean);
+                  median and min are reported; `achieved` uses the mean).
+A plain run does only what that line needs: inputs, the W warm-up steps, the settle phase, the
+K timed steps.  `--full` adds the legs that are not part of the headline:
+  roofline.kernel_ms_without_settle / frac_without_settle: the K steps timed once more, right
+                  after the W warm-ups and before the settle phase;
   "parity":       a REAL comparison of the last timed step's output against the CPU oracle
                   (which units, which tolerance, what error) -- a failed check exits non-zero;
   "cpu_baseline": the reference's CPU path shape timed on this box's host cores on a bounded
                   sample (rank 0, N = 1 only): the C/OpenMP port of the algorithm and, for the
                   4x4 solve, the torch-eager restatement of the reference's op sequence at
                   1 thread and at all threads.
+(`--no-cpu` drops the last two from a --full run.)  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (float32 / float64, rank 0; an output above its share
+of 48 MiB as a fixed sample of its rows): the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 Other workloads (parity-test configs, for profiling): --workload sym_solve6 | batchinv8 |
 nansum | nanmax | sym_invert3 | eig3 | eig8.  `--workload null` is the launcher self-test (no
 computation; runs on CPU with --backend gloo).
@@ -54,7 +62,12 @@ def parse(argv=None):
     p.add_argument('--warmup', type=int, default=10)
     p.add_argument('--workload', default='sym_solve4')
     p.add_argument('--n', type=float, default=None, help='batch per GPU (default: the config size)')
-    p.add_argument('--no-cpu', action='store_true', help='skip the parity + cpu_baseline leg')
+    p.add_argument('--full', action='store_true',
+                   help='also run what the headline does not need: the K steps timed before the settle phase, the '
+                        'parity check against the CPU oracle and the cpu_baseline leg (the last two unless --no-cpu)')
+    p.add_argument('--no-cpu', action='store_true', help='skip the parity + cpu_baseline leg of a --full run')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write the output of the last one as DIR/<name>.npy (rank 0)')
     p.add_argument('--layout', default='aos', choices=['aos', 'soa'])
     p.add_argument('--settle-ms', type=float, default=300.0,
                    help='after the W warm-up steps keep launching (untimed) for this many ms so that the '
@@ -185,6 +198,7 @@ def verdict(got, ref, dn, what, exact_expected=False, scale=None):
 class Workload:
     """name, unit count per step, algorithmic bytes per unit, the step closure, the parity check, the cpu leg."""
     output = None
+    outputs = None          # () -> {name: tensor}: what the last step returned to its caller (--dump-outputs)
     cpu_eager = None
     eager_sizes = (0, 0)
 
@@ -218,6 +232,7 @@ def make_workload(name, n_arg, device, rank, layout):
         w.metric, w.unit = f'{M}x{M} compact-sym solves/sec', 'solves/s'
         w.step = lambda: N.sym_solve(mat, vec, out=out)
         w.output = out
+        w.outputs = lambda: {'x': out}
         kind = {'aos': 1, 'soa': 2}[layout]
         w.kernel = f'rec_kernel<float, SolveOp<float, {M}, 0>, {kind}>'
 
@@ -248,6 +263,7 @@ def make_workload(name, n_arg, device, rank, layout):
         w.metric, w.unit = '3x3 compact-sym inversions/sec', 'inversions/s'
         w.step = lambda: N.sym_invert(mat, out=out)
         w.output = out
+        w.outputs = lambda: {'inverse': out}
         w.kernel = 'rec_kernel<double, InvertOp<double, 3, false>, 1>'
 
         def check():
@@ -278,6 +294,7 @@ def make_workload(name, n_arg, device, rank, layout):
         def step():
             last['out'] = N.eig_sym(a, check_finite=False)
         w.step = step
+        w.outputs = lambda: {'eigenvalues': last['out']}
         w.kernel = f'rec_kernel<float, EigSymOp<float, {E}, false, false>, 1>'
 
         def check():
@@ -313,6 +330,7 @@ def make_workload(name, n_arg, device, rank, layout):
         def step():
             last['out'] = N.batchinv(a)
         w.step = step
+        w.outputs = lambda: {'inverse': last['out']}
         w.kernel = 'rec_kernel<double, BatchInvOp<double, 8>, 1>'
 
         def check():
@@ -349,6 +367,7 @@ def make_workload(name, n_arg, device, rank, layout):
         def step():
             last['out'] = fn(x)
         w.step = step
+        w.outputs = lambda: {name: last['out']}
         w.kernel = f'reduce_all_k1<float, {0 if name == "nansum" else 1}>'
 
         def check():
@@ -455,6 +474,32 @@ def stored_traffic(workload, units, layout):
     return rec.get('hbm_bytes_per_launch'), f'profiles/traffic_{workload}.json (stored rocprofv3 --pmc pass, not this run)'
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: every file of one run together stays below 64 MB
+
+
+def sample_rows(n, k, seed=0):
+    """k sorted row indices out of n, the same on every run: one at a seeded offset in each of k equal strides"""
+    import numpy as np
+    stride = n // k
+    return np.arange(k, dtype=np.int64) * stride + np.random.default_rng(seed).integers(0, stride, k)
+
+
+def dump_outputs(outputs, path):
+    """DIR/<name>.npy of every output of the last timed step, float64 kept, anything else as float32; an output
+    above its share of DUMP_BYTES is written as the rows sample_rows picks (its leading dimension)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    for name, t in outputs.items():
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        row_bytes = (t[0].numel() if t.dim() else 1) * dt.itemsize
+        if t.dim() and t.shape[0] * row_bytes > share:
+            t = t[torch.as_tensor(sample_rows(t.shape[0], max(1, share // row_bytes)), device=t.device)]
+        np.save(os.path.join(path, f'{name}.npy'), t.to(dt).contiguous().cpu().numpy())
+
+
 def census(world, device, dist, comm_device=None):
     """every rank contributes one count and its device identity: proves N ranks on N distinct GPUs"""
     import torch
@@ -539,7 +584,7 @@ def run_rank(a):
     # what the same K steps cost WITHOUT the settle phase below (the first launches after the idle gap of
     # input generation run slower: power-state ramp) -- reported next to the headline, never part of `value`
     cold_ms = None
-    if a.settle_ms > 0 and on_gpu:
+    if a.full and a.settle_ms > 0 and on_gpu:
         c0 = event()
         for _ in range(a.steps):
             w.step()
@@ -572,7 +617,7 @@ def run_rank(a):
     # every rank checks ITS OWN last timed output against the oracle (outside the timed region) and reports its
     # own per-step kernel times, so that an N > 1 line carries parity and a slow point can be attributed
     parity = None
-    if not a.no_cpu and w.check is not None:
+    if a.full and not a.no_cpu and w.check is not None:
         import oracle as O
         O.build()
         O.set_num_threads(max(1, host_cores() // world))
@@ -597,6 +642,8 @@ def run_rank(a):
         if world > 1:
             dist.destroy_process_group()
         return 0
+    if a.dump_outputs:
+        dump_outputs(w.outputs() if w.outputs is not None else {}, a.dump_outputs)
     rc = 0
     distinct = len({(d['uuid'], d['pci'], d['index']) for d in devices})
     value = world * w.units * a.steps / wall
@@ -645,7 +692,7 @@ def run_rank(a):
         if not all(v['ok'] for v in checked) or len(checked) != world:
             print('bench.py: PARITY FAILED against the oracle', file=sys.stderr)
             rc = 4
-    if world == 1 and not a.no_cpu and w.check is not None:
+    if a.full and world == 1 and not a.no_cpu and w.check is not None:
         # the CPU baseline leg (rank 0, one GPU only)
         import oracle as O
         avail = host_cores()
@@ -683,6 +730,9 @@ def main(argv=None):
     a = parse(argv)
     if a.gpus < 1:
         print('bench.py: --gpus must be >= 1', file=sys.stderr)
+        return 2
+    if a.steps < 1:
+        print('bench.py: --steps must be >= 1', file=sys.stderr)
         return 2
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return launch_ranks(a, argv)

@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for w in sym_solve6 batchinv8 nansum nanmax; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc2_${w}_$c -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --workload $w > $O/pmc2_${w}_$c.log 2>&1; echo "pmc $w $c rc=$?"
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc2_${w}_$c -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu --workload $w > $O/pmc2_${w}_$c.log 2>&1; echo "pmc $w $c rc=$?"
   done
 done
 cd $R

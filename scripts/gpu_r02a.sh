@@ -9,15 +9,15 @@ mkdir -p $O
 cd $R
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/pytest_${TAG}.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_${TAG}.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_${TAG}_driver_shape.log 2>&1; echo "bench(driver flags) rc=$?"; tail -1 $O/bench_${TAG}_driver_shape.log | cut -c1-400
+timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_${TAG}_driver_shape.log 2>&1; echo "bench(driver flags) rc=$?"; tail -1 $O/bench_${TAG}_driver_shape.log | cut -c1-400
 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --settle-ms 0 --no-cpu > $O/bench_${TAG}_nosettle.log 2>&1; echo "bench(no settle) rc=$?"; tail -1 $O/bench_${TAG}_nosettle.log | cut -c1-400
 for w in sym_solve4 sym_solve6 batchinv8 sym_invert3 eig3 nansum nanmax; do
-  timeout -k 10 500 python bench.py --steps 100 --warmup 10 --workload $w > $O/bench_${TAG}_$w.log 2>&1; echo "bench $w rc=$?"; tail -1 $O/bench_${TAG}_$w.log | cut -c1-600
+  timeout -k 10 500 python bench.py --full --steps 100 --warmup 10 --workload $w > $O/bench_${TAG}_$w.log 2>&1; echo "bench $w rc=$?"; tail -1 $O/bench_${TAG}_$w.log | cut -c1-600
 done
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --layout soa --no-cpu > $O/bench_${TAG}_sym_solve4_soa.log 2>&1; echo "bench soa rc=$?"; tail -1 $O/bench_${TAG}_sym_solve4_soa.log | cut -c1-400
+timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --layout soa --no-cpu > $O/bench_${TAG}_sym_solve4_soa.log 2>&1; echo "bench soa rc=$?"; tail -1 $O/bench_${TAG}_sym_solve4_soa.log | cut -c1-400
 # eig_sym 3x3: kernel trace, then SQ counter passes (counters in their own runs, program directly after --)
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_eig3 -- python3 $R/bench.py --steps 30 --warmup 5 --no-cpu --workload eig3 > $O/rocprof_${TAG}_eig3.log 2>&1; echo "rocprof eig3 rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_eig3 -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-cpu --workload eig3 > $O/rocprof_${TAG}_eig3.log 2>&1; echo "rocprof eig3 rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --output-format csv -d $O/pmc_${TAG}_eig3_a -- python3 $R/bench.py --steps 3 --warmup 1 --settle-ms 0 --no-cpu --workload eig3 > $O/pmc_${TAG}_eig3_a.log 2>&1; echo "pmc eig3 a rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_THREAD_CYCLES_VALU SQ_INST_CYCLES_VMEM SQ_WAIT_ANY SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_${TAG}_eig3_b -- python3 $R/bench.py --steps 3 --warmup 1 --settle-ms 0 --no-cpu --workload eig3 > $O/pmc_${TAG}_eig3_b.log 2>&1; echo "pmc eig3 b rc=$?"
 cd $R

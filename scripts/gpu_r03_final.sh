@@ -17,20 +17,20 @@ if has tests; then
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_${TAG}.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke_${TAG}.log
 fi
 if has bench; then
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_${TAG}_driver_shape.log 2>&1; echo "bench(driver flags) rc=$?"; tail -1 $O/bench_${TAG}_driver_shape.log | cut -c1-300
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_${TAG}_driver_shape.log 2>&1; echo "bench(driver flags) rc=$?"; tail -1 $O/bench_${TAG}_driver_shape.log | cut -c1-300
   for w in sym_solve4 sym_solve6 batchinv8 sym_invert3 eig3 eig8 nansum nanmax; do
-    timeout -k 10 500 python bench.py --steps 100 --warmup 10 --workload $w > $O/bench_${TAG}_$w.log 2>&1; echo "bench $w rc=$?"; tail -1 $O/bench_${TAG}_$w.log | cut -c1-200
+    timeout -k 10 500 python bench.py --full --steps 100 --warmup 10 --workload $w > $O/bench_${TAG}_$w.log 2>&1; echo "bench $w rc=$?"; tail -1 $O/bench_${TAG}_$w.log | cut -c1-200
   done
   # channel-first (SoA) against AoS at the medium and the full batch (verdict item: the 17 % gap of the layouts table)
   for lay in aos soa; do for nn in 1.7e7 1e8; do for w in sym_solve4 sym_solve6; do
-    timeout -k 10 300 python bench.py --steps 100 --warmup 10 --layout $lay --n $nn --no-cpu --workload $w > $O/bench_${TAG}_${w}_${lay}_${nn}.log 2>&1; echo "bench $w $lay $nn rc=$?"
+    timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --layout $lay --n $nn --no-cpu --workload $w > $O/bench_${TAG}_${w}_${lay}_${nn}.log 2>&1; echo "bench $w $lay $nn rc=$?"
   done; done; done
-  timeout -k 10 300 python bench.py --gpus 3 --steps 20 --warmup 5 --n 2e7 --backend gloo --share-gpu > $O/bench_${TAG}_rehearsal3.log 2>&1; echo "rehearsal rc=$?"
+  timeout -k 10 300 python bench.py --full --gpus 3 --steps 20 --warmup 5 --n 2e7 --backend gloo --share-gpu > $O/bench_${TAG}_rehearsal3.log 2>&1; echo "rehearsal rc=$?"
 fi
 if has prof; then
   cd /tmp && export TMPDIR=/tmp
   for w in sym_solve4 sym_solve6 batchinv8 eig3 eig8 nansum; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_$w -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu --workload $w > $O/rocprof_${TAG}_$w.log 2>&1; echo "rocprof $w rc=$?"
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${TAG}_$w -- python3 $R/bench.py --full --steps 100 --warmup 10 --no-cpu --workload $w > $O/rocprof_${TAG}_$w.log 2>&1; echo "rocprof $w rc=$?"
   done
   cd $R
   for w in sym_solve4 sym_solve6 batchinv8 eig3 eig8 nansum; do

@@ -128,3 +128,23 @@ def test_no_constant_parity_in_bench_or_profiles():
     (round-1 finding)"""
     src = open(BENCH).read()
     assert 'lambda: (0.0, True)' not in src and 'w.check = lambda' not in src
+
+
+def test_dump_outputs_is_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: float64 stays float64, other outputs become float32, a scalar stays 0-d; an output above its share of the
+    budget is written as the same seeded rows on every run, and every file of a run together stays below 64 MB"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.sample_rows(10 ** 8, 1000), bench.sample_rows(10 ** 8, 1000))
+    idx = bench.sample_rows(10 ** 8, 1000)
+    assert (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < 10 ** 8
+    big = torch.randn(200_000, 8, 8, dtype=torch.float64)
+    small = torch.arange(12, dtype=torch.int32).reshape(3, 4)
+    bench.dump_outputs({'inverse': big, 'small': small, 'scalar': torch.tensor(2.5, dtype=torch.float16)}, tmp_path)
+    inv, sm, sc = (np.load(tmp_path / f'{k}.npy') for k in ('inverse', 'small', 'scalar'))
+    assert inv.dtype == np.float64 and sm.dtype == np.float32 and sc.dtype == np.float32 and sc.shape == () and float(sc) == 2.5
+    assert np.array_equal(inv, big.numpy()[bench.sample_rows(200_000, inv.shape[0])])
+    assert np.array_equal(sm, small.numpy())
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) < 64e6
