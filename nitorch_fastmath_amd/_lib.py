@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (kernel experiments load another build of the library: honoured only under NFM_DEBUG, the one variable the
-# product reads; the row-wave measurement knobs of nfm_rowwave.hip sit behind the same gate)
+# product reads; the C++ library reads none)
 LIB_PATH = (os.environ.get('NFM_HIP_LIB') if os.environ.get('NFM_DEBUG') else None) or os.path.join(_HERE, 'libnfm_hip.so')
 
 F32, F64 = 0, 1

@@ -1,10 +1,9 @@
 // nfm_batched.hip -- general small matrices: batchinv / batchdet / batchmatvec
 // (reference `_impl/batched.py`).  One matrix per lane; N <= 3 use the reference's
 // adjugate closed forms, 4 <= N <= 8 Gauss-Jordan / LU with partial pivoting in
-// registers, N > 8 the LDS-resident kernels of nfm_big.hpp.
+// registers, N > 8 the chains of batch_inv_t / batch_det_t.
 #include "nfm_batched_ops.hpp"
 #include "nfm_big.hpp"
-#include "nfm_large.hpp"
 #include "nfm_rowwave.hpp"
 #include "nfm_spd.hpp"
 
@@ -29,21 +28,18 @@ namespace nfm {
         return NFM_ESIZE;          \
     }
 
+// Orders 9..16: contiguous row-major matrices go to the diagonal-pivots-first kernels of nfm_spd.hip (float32
+// 9..16, float64 9..13: gen_fits), which hand the wavefronts that need a row exchange to the pivoted elimination;
+// float64 14..16 do not fit a lane there and take one matrix per 16 lanes (nfm_rowwave.hip).  Any other layout:
+// the LDS-resident kernels of nfm_big.hpp.
 template <typename T>
 static int batch_inv_t(int N, int flags, int64_t no, int64_t ni, const nfm_operand *a, const nfm_operand *out,
                        void *stream)
 {
     if (N > 8) {
-        if (no == 1) { // diagonal pivots first, the pivoted elimination for the wavefronts that need it (nfm_spd.hip)
-            const int rc = Spd<T>::batch_inv(N, ni, a, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
-        if (no == 1 && rowwave_first<T>(N, RWW_INV_GEN)) { // one matrix per 16 lanes (nfm_rowwave.hip)
-            const int rc = RowWave<T>::batch_inv(N, ni, a, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
         if (no == 1) {
-            const int rc = Large<T>::batch_inv(N, ni, a, out, stream);
+            int rc = Spd<T>::batch_inv(N, ni, a, out, stream);
+            if (rc == NFM_EFALLBACK) rc = RowWave<T>::batch_inv(N, ni, a, out, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
         return big_batch_inv<T>(N, no, ni, a, out, stream);
@@ -53,20 +49,14 @@ static int batch_inv_t(int N, int flags, int64_t no, int64_t ni, const nfm_opera
     return NFM_EINVAL;
 }
 
+// orders 9..16: as batch_inv_t
 template <typename T>
 static int batch_det_t(int N, int64_t no, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
 {
     if (N > 8) {
-        if (no == 1) { // diagonal pivots first (nfm_spd.hip)
-            const int rc = Spd<T>::batch_det(N, ni, a, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
-        if (no == 1 && rowwave_first<T>(N, RWW_DET_GEN)) {
-            const int rc = RowWave<T>::batch_det(N, ni, a, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
         if (no == 1) {
-            const int rc = Large<T>::batch_det(N, ni, a, out, stream);
+            int rc = Spd<T>::batch_det(N, ni, a, out, stream);
+            if (rc == NFM_EFALLBACK) rc = RowWave<T>::batch_det(N, ni, a, out, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
         return big_batch_det<T>(N, no, ni, a, out, stream);

@@ -390,24 +390,29 @@ struct SoaIO {
 };
 
 // ------------------------------------------------------------------ host side
-// Can the operand take the LDS-transposed path?  It must be a single contiguous
-// batch-major block: records of C elements back to back, 16-byte aligned base.
-inline bool tile_ok(const nfm_operand *op, int C, int rows, int cols, int64_t n_outer, int64_t n_inner,
-                    size_t elem)
+// Is the operand one contiguous batch-major block?  Records of `rec` elements back to back, each a
+// row-major rows x cols matrix (rows == 1: a vector of rec elements), at an element-aligned base.
+// The layout every kernel that streams whole tiles of records assumes (tile_ok below, nfm_spd.hip,
+// nfm_rowwave.hip).
+inline bool contiguous_records(const nfm_operand *op, int64_t rec, int rows, int cols, size_t elem)
 {
-    if (op->ptr == nullptr) return false;
-    // any element-aligned base: the tile's 16-byte global accesses only need dword alignment
+    if (op == nullptr || op->ptr == nullptr) return false;
+    // any element-aligned base: the tiles' 16-byte global accesses only need dword alignment
     // (VecOf::gtype; measured: a base 4 bytes off a 16-byte line streams at the aligned rate,
     // 5.85 vs 5.63 TB/s for the 4x4 solve, profiles/r02/layouts_table.md)
     if (reinterpret_cast<uintptr_t>(op->ptr) % elem != 0) return false;
-    if (n_outer != 1) return false; // the facade collapses contiguous outer levels into one
-    if (op->stride_inner != C) return false;
-    if (rows > 1) {
-        if (op->stride_row != cols || op->stride_col != 1) return false;
-    } else if (C > 1 && op->stride_col != 1) {
-        return false;
-    }
-    return true;
+    if (op->stride_inner != rec) return false;
+    if (rows > 1) return op->stride_row == cols && op->stride_col == 1;
+    return rec <= 1 || op->stride_col == 1;
+}
+
+// Can the operand take the LDS-transposed path?  It must be a single contiguous
+// batch-major block: records of C elements back to back.
+inline bool tile_ok(const nfm_operand *op, int C, int rows, int cols, int64_t n_outer, int64_t n_inner,
+                    size_t elem)
+{
+    // (the facade collapses contiguous outer levels into one)
+    return n_outer == 1 && contiguous_records(op, C, rows, cols, elem);
 }
 
 // Can the operand be moved with one packed 4/8/16-byte access per lane?  Records back

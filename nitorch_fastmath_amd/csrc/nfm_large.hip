@@ -1,14 +1,15 @@
 // nfm_large.hip -- register-resident kernels for orders 9..16 (see nfm_large.hpp).
-// Compiled 32 times (-DNFM_LARGE_PART=0..31), one object per (function group, dtype, quarter
-// of the order range), so that the big fully-unrolled eliminations build in parallel:
-// PART = group * 8 + dtype * 4 + quarter; quarter q holds orders 9+2q and 10+2q.
+// Compiled 24 times (-DNFM_LARGE_PART=0..23), one object per (function, dtype, quarter of the
+// order range), so that the big fully-unrolled eliminations build in parallel:
+// PART = function * 8 + dtype * 4 + quarter; quarter q holds orders 9+2q and 10+2q;
+// function 0: sym_solve, 1: sym_invert, 2: sym_matvec.
 #include "nfm_sym_ops.hpp"
 #include "nfm_batched_ops.hpp"
 #include "nfm_large.hpp"
 #include "nfm_rowwave.hpp"
 
 #ifndef NFM_LARGE_PART
-#error "compile with -DNFM_LARGE_PART=0..31"
+#error "compile with -DNFM_LARGE_PART=0..23"
 #endif
 
 #define NFM_LGROUP (NFM_LARGE_PART / 8)
@@ -40,14 +41,16 @@ namespace nfm {
     switch (Nexpr) { NFM_LCASE(15, __VA_ARGS__) NFM_LCASE(16, __VA_ARGS__) default: break; }
 #endif
 
-// Every op covers the orders 9..16 of both dtypes that rowwave_choice (nfm_rowwave.hpp) leaves
-// to the lane-per-matrix form; the others (the ones that did not fit the register file) answer
-// NFM_EFALLBACK without instantiating a kernel.  The pivoting code uses OPAQUE selects here
+// The factorisations cover the orders 9..16 of both dtypes that rowwave_choice (nfm_rowwave.hpp)
+// leaves to the lane-per-matrix form; the others (the ones that did not fit the register file)
+// answer NFM_EFALLBACK without instantiating a kernel.  Only pivoting='always' reaches them: every
+// other contiguous record goes to the no-exchange-first kernels of nfm_spd.hip (which also take
+// every contiguous sym_det / batchinv / batchdet).  The pivoting code uses OPAQUE selects here
 // (Sel<true>, nfm_smallmat.hpp): no data-dependent control flow is left, so whatever spill
 // code the big eliminations need runs under a full EXEC mask, and most kernels need none
 // (-Rpass-analysis=kernel-resource-usage: every f32 kernel and f64 up to 13 are spill-free).
-//   inverse (compact symmetric and general): LU + column-by-column unit solves (InvStreamOp)
-//   solve / determinants: Gaussian elimination with partial pivoting (SolveOp, DetOp, BatchDetOp)
+//   inverse: LU + column-by-column unit solves (InvStreamOp)
+//   solve: Gaussian elimination with partial pivoting (SolveOp)
 // tests/test_gpu_large_orders.py checks every order of every op against the CPU restatement
 // on thousands of matrices, twice.
 
@@ -74,13 +77,6 @@ int NFM_LNAME(sym_solve)(int M, int64_t ni, const nfm_operand *mat, const nfm_op
                      return (rec_launch<TL, SolveOp<TL, N, NFM_MAT_SYM>, true>(mat, vec, nullptr, out, 1, ni, p, stream)))
     return NFM_EFALLBACK;
 }
-int NFM_LNAME(sym_det)(int M, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream)
-{
-    NoParams p{0};
-    NFM_LSWITCH16(M, if constexpr (NFM_LKEEP(N, RWW_DET_SYM))
-                     return (rec_launch<TL, DetOp<TL, N>, true>(mat, nullptr, nullptr, out, 1, ni, p, stream)))
-    return NFM_EFALLBACK;
-}
 #endif
 
 #if NFM_LGROUP == 1
@@ -94,28 +90,11 @@ int NFM_LNAME(sym_invert)(int M, int64_t ni, const nfm_operand *mat, const nfm_o
 #endif
 
 #if NFM_LGROUP == 2
-int NFM_LNAME(batch_inv)(int N_, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
-{
-    InvParams p{0};
-    NFM_LSWITCH16(N_, if constexpr (NFM_LKEEP(N, RWW_INV_GEN))
-                      return (rec_launch<TL, InvStreamOp<TL, N, false>, true>(a, nullptr, nullptr, out, 1, ni, p, stream)))
-    return NFM_EFALLBACK;
-}
-#endif
-
-#if NFM_LGROUP == 3
 int NFM_LNAME(sym_matvec)(int M, int mode, int64_t ni, const nfm_operand *mat, const nfm_operand *vec,
                           const nfm_operand *inp, const nfm_operand *out, void *stream)
 {
     MatvecParams p{mode};
     NFM_LSWITCH16(M, return (rec_launch<TL, MatvecOp<TL, N, NFM_MAT_SYM>, true>(mat, vec, inp, out, 1, ni, p, stream)))
-    return NFM_EFALLBACK;
-}
-int NFM_LNAME(batch_det)(int N_, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
-{
-    NoParamsB p{0};
-    NFM_LSWITCH16(N_, if constexpr (NFM_LKEEP(N, RWW_DET_GEN))
-                      return (rec_launch<TL, BatchDetOp<TL, N>, true>(a, nullptr, nullptr, out, 1, ni, p, stream)))
     return NFM_EFALLBACK;
 }
 #endif

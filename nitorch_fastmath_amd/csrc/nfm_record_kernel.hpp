@@ -276,20 +276,13 @@ struct op_no_tile<Op, std::void_t<decltype(Op::kNoTile)>> : std::bool_constant<O
 // Orders 9..16, one matrix per lane: which kernels fetch their records per lane instead of through the LDS
 // transpose (op_no_tile, nfm_record_kernel.hpp).  Without the LDS image some of them gain a wavefront per
 // SIMD (12x12 float32 solve: 257 -> 254 VGPRs, 1 -> 2 waves: 1.6x), others lose the coalescing for nothing;
-// measured case by case on one box with two builds of the library (scripts/gpu_ab_large.sh,
-// profiles/r02/large_no_tile_ab.md) -- the cases where the no-tile build won by more than 5 %.
-enum { LN_SOLVE = 0, LN_DET = 1, LN_BDET = 2 };
-__host__ __device__ constexpr bool large_no_tile(bool f64, int N, int what)
+// measured case by case on one box with two builds of the library (profiles/r02/large_no_tile_ab.md) --
+// the cases where the no-tile build won by more than 5 %.  Of the Ops measured, only the solve is still
+// compiled at these orders (nfm_large.hip).
+__host__ __device__ constexpr bool large_no_tile_solve(bool f64, int N)
 {
     if (N < 9) return false;
-    if (!f64) {
-        if (what == LN_SOLVE) return N >= 10 && N <= 14;
-        if (what == LN_DET) return N <= 15;
-        return N >= 12 && N <= 15; // LN_BDET
-    }
-    if (what == LN_SOLVE) return N <= 10;
-    if (what == LN_DET) return N >= 10 && N <= 13;
-    return N >= 10 && N <= 12; // LN_BDET
+    return f64 ? N <= 10 : N >= 10 && N <= 14;
 }
 
 // mode of an operand in the compile-time (KIND_AOS) kernel: its preferred one, or for a no-tile Op the
@@ -329,12 +322,10 @@ struct KindTile {
 // Component runs that do not start on 16-byte boundaries (odd voxel counts) pay per tile for the
 // two straddling vectors of every component: 512-lane tiles halve that (4x4 solve: +7 %), while
 // aligned runs are better off at 256 (-4 % at 512).  Only Ops whose SoA image fits 80 KiB (6x6: +8 %).
+constexpr int kSoawLdsLimit = 80 * 1024; // two 512-lane workgroups per CU
 template <typename T, class Op>
 struct KindTile<T, Op, KIND_SOAW> {
-#ifndef NFM_SOAW_LIMIT
-#define NFM_SOAW_LIMIT (80 * 1024) // two 512-lane workgroups per CU
-#endif
-    static constexpr int value = (Op::TILE == 256 && RecLayout<T, Op, 512>::gtotal <= NFM_SOAW_LIMIT) ? 512 : Op::TILE;
+    static constexpr int value = (Op::TILE == 256 && RecLayout<T, Op, 512>::gtotal <= kSoawLdsLimit) ? 512 : Op::TILE;
 };
 
 // NFM_REC_KERNEL_ATTR: extra kernel attributes of a translation unit (the orders 9..16 of the QR family ask for

@@ -24,7 +24,7 @@
 //   * HBM traffic: the tile's records are contiguous, so they are streamed with 16-byte accesses
 //     through an LDS image (rows padded to an odd number of 16-byte slots), exactly the
 //     algorithmic bytes; a base that is only element-aligned takes element accesses.
-//   The form (R, LB) of every (dtype, order, op) is rowwave_choice (nfm_rowwave.hpp).
+//   The form (R, LB) of every (dtype, order, op) is rowwave_choice (nfm_rowwave.hpp); only that form is compiled.
 //
 // 1 / pivot is v_rcp + Newton steps (2 for float64, 1 for float32: <= 1.5 ulp) instead of the
 // IEEE division sequence; pivots are the same as the CPU restatement's (partial pivoting, first
@@ -34,34 +34,10 @@
 // Reference paths replaced: `torch.linalg.solve` of the densified matrix (`_impl/sym.py:392-396`),
 // `a.inverse()` / `a.det()` (`_impl/batched.py:119-120`, `:53-54`).
 #include "nfm_rowwave_core.hpp"
+#include "nfm_spd.hpp"
 
 namespace nfm {
 namespace roww {
-
-// contiguous batch-major records (what the facade allocates; the base need not be 16-byte aligned)
-static bool rec_contig(const nfm_operand *o, int64_t rec, int rows, int cols, size_t elem)
-{
-    if (o == nullptr || o->ptr == nullptr) return false;
-    if (reinterpret_cast<uintptr_t>(o->ptr) % elem != 0) return false;
-    if (o->stride_inner != rec) return false;
-    if (cols > 1 && o->stride_col != 1) return false;
-    if (rows > 1 && o->stride_row != cols) return false;
-    return true;
-}
-
-template <typename T, int N, int OP, int R, bool LB>
-static int launch_r(const void *a, const void *b, void *o, int64_t n, const RowParams<T> &p, void *stream)
-{
-    constexpr size_t lds = tile_lds_bytes<T, N, OP, LB>();
-    static_assert(lds <= 64 * 1024, "row-wave tile must fit the default dynamic LDS limit");
-    if (n == 0) return NFM_OK;
-    const int64_t nblk = (n + MPB - 1) / MPB;
-    if (nblk > 0x7fffffffLL) return NFM_ESIZE;
-    hipLaunchKernelGGL((roww_kernel<T, N, OP, R, LB>), dim3((unsigned)nblk), dim3(256 / R), lds,
-                       static_cast<hipStream_t>(stream), static_cast<const T *>(a), static_cast<const T *>(b),
-                       static_cast<T *>(o), n, p);
-    return launch_status();
-}
 
 constexpr int rww_of(int op)
 {
@@ -69,24 +45,35 @@ constexpr int rww_of(int op)
            : op == RW_DET_SYM ? RWW_DET_SYM : op == RW_INV_GEN ? RWW_INV_GEN : RWW_DET_GEN;
 }
 
-// form of the kernel: rowwave_choice (nfm_rowwave.hpp); NFM_ROWWAVE_ROWS (1 / 2 / 4) and
-// NFM_ROWWAVE_LDS (0 / 1) override it for the side-by-side measurements
+// The cases the dispatchers (nfm_sym.hip, nfm_batched.hip) can send here: the ones rowwave_choice gives a form, and
+// of the general matrices only those the no-exchange kernels of nfm_spd.hip do not hold in a lane (gen_fits: float64
+// 14..16) -- every other contiguous general matrix is taken there first.  The others compile no kernel.
+template <typename T, int N, int OP>
+constexpr bool reached()
+{
+    constexpr bool f64 = sizeof(T) == 8;
+    if (rowwave_choice(f64, N, rww_of(OP)).rows == 0) return false;
+    return (OP != RW_INV_GEN && OP != RW_DET_GEN) || !gen_fits(f64, N, OP == RW_INV_GEN);
+}
+
+// the form of the kernel: rowwave_choice (nfm_rowwave.hpp)
 template <typename T, int N, int OP>
 static int launch(const void *a, const void *b, void *o, int64_t n, const RowParams<T> &p, void *stream)
 {
-    static const int rows = [] { const char *e = dbg_env("NFM_ROWWAVE_ROWS"); return e ? atoi(e) : 0; }();
-    static const int ldsb = [] { const char *e = dbg_env("NFM_ROWWAVE_LDS"); return e ? atoi(e) : -1; }();
-    constexpr RwChoice c = rowwave_choice(sizeof(T) == 8, N, rww_of(OP));
-    const int r = rows ? rows : (c.rows ? c.rows : 2);
-    const bool lb = ldsb >= 0 ? ldsb != 0 : c.lds;
-    if (lb) {
-        if (r == 1) return launch_r<T, N, OP, 1, true>(a, b, o, n, p, stream);
-        if (r == 4) return launch_r<T, N, OP, 4, true>(a, b, o, n, p, stream);
-        return launch_r<T, N, OP, 2, true>(a, b, o, n, p, stream);
+    if constexpr (!reached<T, N, OP>()) {
+        return NFM_EFALLBACK_RW;
+    } else {
+        constexpr RwChoice c = rowwave_choice(sizeof(T) == 8, N, rww_of(OP));
+        constexpr size_t lds = tile_lds_bytes<T, N, OP, c.lds>();
+        static_assert(lds <= 64 * 1024, "row-wave tile must fit the default dynamic LDS limit");
+        if (n == 0) return NFM_OK;
+        const int64_t nblk = (n + MPB - 1) / MPB;
+        if (nblk > 0x7fffffffLL) return NFM_ESIZE;
+        hipLaunchKernelGGL((roww_kernel<T, N, OP, c.rows, c.lds>), dim3((unsigned)nblk), dim3(256 / c.rows), lds,
+                           static_cast<hipStream_t>(stream), static_cast<const T *>(a), static_cast<const T *>(b),
+                           static_cast<T *>(o), n, p);
+        return launch_status();
     }
-    if (r == 1) return launch_r<T, N, OP, 1, false>(a, b, o, n, p, stream);
-    if (r == 4) return launch_r<T, N, OP, 4, false>(a, b, o, n, p, stream);
-    return launch_r<T, N, OP, 2, false>(a, b, o, n, p, stream);
 }
 
 #define NFM_RW_SWITCH(Nexpr, ...)                                                                  \
@@ -111,8 +98,8 @@ int RowWave<T>::sym_solve(int M, int64_t ni, const nfm_operand *mat, const nfm_o
                           const double *eps, void *stream)
 {
     const int K = M * (M + 1) / 2;
-    if (!rec_contig(mat, K, 1, K, sizeof(T)) || !rec_contig(vec, M, 1, M, sizeof(T)) ||
-        !rec_contig(out, M, 1, M, sizeof(T)))
+    if (!contiguous_records(mat, K, 1, K, sizeof(T)) || !contiguous_records(vec, M, 1, M, sizeof(T)) ||
+        !contiguous_records(out, M, 1, M, sizeof(T)))
         return NFM_EFALLBACK_RW;
     RowParams<T> p;
     p.has_eps = eps != nullptr;
@@ -127,7 +114,8 @@ int RowWave<T>::sym_invert(int M, int diag_only, int64_t ni, const nfm_operand *
 {
     const int K = M * (M + 1) / 2;
     const int RO = diag_only ? M : K;
-    if (!rec_contig(mat, K, 1, K, sizeof(T)) || !rec_contig(out, RO, 1, RO, sizeof(T))) return NFM_EFALLBACK_RW;
+    if (!contiguous_records(mat, K, 1, K, sizeof(T)) || !contiguous_records(out, RO, 1, RO, sizeof(T)))
+        return NFM_EFALLBACK_RW;
     RowParams<T> p{};
     if (diag_only) {
         NFM_RW_SWITCH(M, return (launch<T, N, RW_INVDIAG_SYM>(mat->ptr, nullptr, out->ptr, ni, p, stream)))
@@ -138,20 +126,10 @@ int RowWave<T>::sym_invert(int M, int diag_only, int64_t ni, const nfm_operand *
 }
 
 template <typename T>
-int RowWave<T>::sym_det(int M, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream)
-{
-    const int K = M * (M + 1) / 2;
-    if (!rec_contig(mat, K, 1, K, sizeof(T)) || out == nullptr || out->ptr == nullptr || out->stride_inner != 1)
-        return NFM_EFALLBACK_RW;
-    RowParams<T> p{};
-    NFM_RW_SWITCH(M, return (launch<T, N, RW_DET_SYM>(mat->ptr, nullptr, out->ptr, ni, p, stream)))
-    return NFM_EFALLBACK_RW;
-}
-
-template <typename T>
 int RowWave<T>::batch_inv(int Nn, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
 {
-    if (!rec_contig(a, (int64_t)Nn * Nn, Nn, Nn, sizeof(T)) || !rec_contig(out, (int64_t)Nn * Nn, Nn, Nn, sizeof(T)))
+    const int64_t rec = (int64_t)Nn * Nn;
+    if (!contiguous_records(a, rec, Nn, Nn, sizeof(T)) || !contiguous_records(out, rec, Nn, Nn, sizeof(T)))
         return NFM_EFALLBACK_RW;
     RowParams<T> p{};
     NFM_RW_SWITCH(Nn, return (launch<T, N, RW_INV_GEN>(a->ptr, nullptr, out->ptr, ni, p, stream)))
@@ -161,7 +139,7 @@ int RowWave<T>::batch_inv(int Nn, int64_t ni, const nfm_operand *a, const nfm_op
 template <typename T>
 int RowWave<T>::batch_det(int Nn, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
 {
-    if (!rec_contig(a, (int64_t)Nn * Nn, Nn, Nn, sizeof(T)) || out == nullptr || out->ptr == nullptr ||
+    if (!contiguous_records(a, (int64_t)Nn * Nn, Nn, Nn, sizeof(T)) || out == nullptr || out->ptr == nullptr ||
         out->stride_inner != 1)
         return NFM_EFALLBACK_RW;
     RowParams<T> p{};
@@ -173,14 +151,6 @@ int RowWave<T>::batch_det(int Nn, int64_t ni, const nfm_operand *a, const nfm_op
 template struct RowWave<double>;
 #else
 template struct RowWave<float>;
-
-bool rowwave_forced(bool f64, int N)
-{
-    static const int env64 = [] { const char *e = dbg_env("NFM_ROWWAVE_MIN_F64"); return e ? atoi(e) : 0; }();
-    static const int env32 = [] { const char *e = dbg_env("NFM_ROWWAVE_MIN_F32"); return e ? atoi(e) : 0; }();
-    const int m = f64 ? env64 : env32;
-    return m > 0 && N >= m;
-}
 #endif
 
 } // namespace nfm

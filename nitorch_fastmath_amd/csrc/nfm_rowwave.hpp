@@ -1,6 +1,7 @@
 // nfm_rowwave.hpp -- front end of the one-matrix-per-16-lanes kernels (nfm_rowwave.hip) for
-// orders 9..16 on contiguous batch-major operands.  Every function answers NFM_EFALLBACK_ when
-// the order or the layout is not covered; the caller then takes the lane-per-matrix kernels of
+// orders 9..16 on contiguous batch-major operands.  Every function answers NFM_EFALLBACK_RW when
+// the order or the layout is not covered, or when the case is one the dispatchers never send here
+// (no kernel is compiled for it); the caller then takes the lane-per-matrix kernels of
 // nfm_large.hip / the LDS-resident ones of nfm_big.hpp.
 #pragma once
 #include "nfm_common.hpp"
@@ -15,7 +16,6 @@ struct RowWave {
                          const double *eps, void *stream);
     static int sym_invert(int M, int diag_only, int64_t ni, const nfm_operand *mat, const nfm_operand *out,
                           void *stream);
-    static int sym_det(int M, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream);
     static int batch_inv(int N, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream);
     static int batch_det(int N, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream);
 };
@@ -52,15 +52,6 @@ constexpr RwChoice rowwave_choice(bool f64, int N, int what)
     case RWW_DET_GEN: return N >= 16 ? RwChoice{2, false} : RwChoice{0, false};
     default: return {0, false};
     }
-}
-// run-time form for the dispatchers (nfm_sym.hip, nfm_batched.hip).  NFM_ROWWAVE_MIN_F64 / _F32
-// (environment, read once per process) force every order >= the value onto the row-wave kernels:
-// scripts/bench_rowwave.py uses it to time the forms side by side.
-bool rowwave_forced(bool f64, int N);
-template <typename T>
-inline bool rowwave_first(int N, int what)
-{
-    return rowwave_choice(sizeof(T) == 8, N, what).rows != 0 || rowwave_forced(sizeof(T) == 8, N);
 }
 
 } // namespace nfm

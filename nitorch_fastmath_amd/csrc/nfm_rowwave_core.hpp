@@ -1,7 +1,6 @@
 // nfm_rowwave_core.hpp -- the device side of the one-matrix-per-16-lanes kernels (nfm_rowwave.hip documents the
 // algorithm): shared with nfm_spd.hip, whose wavefronts fall back to it.
 #pragma once
-#include <stdlib.h>
 #include "nfm_common.hpp"
 #include "nfm_smallmat.hpp"
 #include "nfm_rowwave.hpp"
@@ -10,14 +9,6 @@ namespace nfm {
 namespace roww {
 
 constexpr int MPB = 16; // matrices per workgroup
-
-// The measurement knobs of this file (scripts/bench_rowwave.py: force a form, force the row-wave kernels from an
-// order up) are read only when NFM_DEBUG is set in the environment: the product's dispatch depends on ONE variable.
-static const char *dbg_env(const char *name)
-{
-    static const bool on = getenv("NFM_DEBUG") != nullptr;
-    return on ? getenv(name) : nullptr;
-}
 
 enum { RW_SOLVE_SYM = 0, RW_INV_SYM, RW_INVDIAG_SYM, RW_DET_SYM, RW_INV_GEN, RW_DET_GEN };
 

@@ -32,27 +32,16 @@
 #ifndef NFM_SPD_PART
 #error "compile with -DNFM_SPD_PART=0..7"
 #endif
-#ifndef NFM_GEN_F64_MAX_INV
-#define NFM_GEN_F64_MAX_INV 13 // largest float64 orders of the general no-exchange kernels (N^2 doubles per lane + staging)
-#define NFM_GEN_F64_MAX_DET 13
-#endif
 
 namespace nfm {
 namespace spd {
 
 using roww::RowParams;
 
-// rows per lane of the fallback (FR; 16 / FR lanes per matrix, 4 FR matrices per pass).  4 in both dtypes: with one
-// row per lane (16 passes of 4 matrices) a float64 batch in which every matrix is indefinite ran 5x behind the
-// pivoted kernels alone
-#ifndef NFM_SPD_FR64
-#define NFM_SPD_FR64 4
-#endif
-template <typename T>
-constexpr int fallback_rows()
-{
-    return sizeof(T) == 8 ? NFM_SPD_FR64 : 4;
-}
+// rows per lane of the fallback (FR; 16 / FR lanes per matrix, FM = 4 FR matrices per pass, the GROUP a wavefront
+// votes on).  4 in both dtypes: with one row per lane (16 passes of 4 matrices) a float64 batch in which every matrix
+// is indefinite ran 5x behind the pivoted kernels alone
+constexpr int kFallbackRows = 4;
 
 constexpr int roww_op(int op)
 {
@@ -303,7 +292,7 @@ template <typename T, int N, int OP>
 constexpr size_t spd_lds_bytes()
 {
     constexpr int ROUT = OP == SP_SOLVE ? N : OP == SP_INV ? sym_k(N) : OP == SP_INVDIAG ? N : 1;
-    size_t b = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * fallback_rows<T>()>();
+    size_t b = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * kFallbackRows>();
     if (!spd_tiled<T, N>() && OP == SP_INV) {
         const size_t t = TileIO<T, sym_k(N), 32>::kLdsBytes; // SubOut<T, K, 2>
         b = b > t ? b : t;
@@ -368,7 +357,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, spd_max_waves<T, N>()))) __laun
     // the vote.  Matrices go to the fallback in groups of FM = what one of its passes works on; every other lane of
     // the wavefront finishes and stores as if nothing had happened (the groups of the bad matrices store nothing: an
     // in-place call must leave their input for the fallback)
-    constexpr int FR = fallback_rows<T>(), FM = 4 * FR, NG = 64 / FM;
+    constexpr int FR = kFallbackRows, FM = 4 * FR, NG = 64 / FM;
     const unsigned long long badl = __ballot(!ok);
     unsigned bad = 0;
     if (__builtin_expect(badl != 0, 0)) {
@@ -412,8 +401,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, spd_max_waves<T, N>()))) __laun
     }
     // not positive definite somewhere in this wavefront: the pivoted elimination of nfm_rowwave on the groups that
     // hold such a matrix, FR rows per lane = FM matrices per pass (a pass reads its records before it writes: in-place
-    // calls are safe).  float32: 4 rows per lane, up to 4 passes; float64: one row per lane, up to 16 passes -- 4 rows
-    // of 16 doubles are 128 registers before anything else.
+    // calls are safe): 4 rows per lane, up to 4 passes.
 #pragma unroll 1
     for (int pass = 0; pass < NG; ++pass) {
         const int64_t m0 = tile0 + FM * pass;
@@ -474,7 +462,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, spd_max_waves<T, N>()))) __laun
     }
     T det;
     const bool ok = ldl_factor<T, N>(m, det);
-    constexpr int FR = fallback_rows<T>(), FM = 4 * FR, NG = 64 / FM;
+    constexpr int FR = kFallbackRows, FM = 4 * FR, NG = 64 / FM;
     const unsigned long long badl = __ballot(!ok);
     unsigned bad = 0;
     if (__builtin_expect(badl != 0, 0)) {
@@ -521,7 +509,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, spd_max_waves<T, N>()))) __laun
 template <typename T, int N, int OP>
 static int launch_strided(const SOp &a, const SOp &b, const SOp &o, int64_t no, int64_t n, const RowParams<T> &p, void *stream)
 {
-    constexpr size_t lds = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * fallback_rows<T>()>();
+    constexpr size_t lds = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * kFallbackRows>();
     static_assert(lds <= 64 * 1024, "the fallback's tile must fit the default dynamic LDS limit");
     if (n == 0 || no == 0) return NFM_OK;
     const int64_t nblk = (n + 63) / 64;
@@ -687,7 +675,7 @@ constexpr int gen_max_waves()
 template <typename T, int N, int OP>
 constexpr size_t gen_lds_bytes()
 {
-    size_t b = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * fallback_rows<T>()>();
+    size_t b = roww::tile_lds_bytes<T, N, roww_op(OP), false, 4 * kFallbackRows>();
     const size_t t = SubOut<T, N * N, gen_out_subs<T, N>()>::kLdsBytes; // (the way in uses the same geometry)
     b = b > t ? b : t;
     return b;
@@ -713,7 +701,7 @@ __global__ __attribute__((amdgpu_waves_per_eu(1, gen_max_waves<T, N>()))) __laun
     for (int r = 0; r < N; ++r)
 #pragma unroll
         for (int c = 0; c < N; ++c) a[r][c] = f[r * N + c];
-    constexpr int FR = fallback_rows<T>(), FM = 4 * FR, NG = 64 / FM;
+    constexpr int FR = kFallbackRows, FM = 4 * FR, NG = 64 / FM;
     bool ok;
     T det = T(0);
     if constexpr (OP == SP_GDET) det = lu_det_nopivot<T, N>(a, ok);
@@ -763,6 +751,8 @@ __global__ __launch_bounds__(128) void redo_kernel(const T *__restrict__ A, cons
                                                    int64_t n, RowParams<T> p)
 {
     constexpr int CH = 16; // groups per workgroup (64: a batch of indefinite matrices ran 64 tiles in a row per workgroup, too few in flight)
+    // (the first launch marks groups of FM = 4 * kFallbackRows matrices; this one reads and redoes groups of 16)
+    static_assert(4 * kFallbackRows == 16, "mark groups and redo groups must be the same 16 matrices");
     constexpr int ROUT = OP == SP_SOLVE ? N : OP == SP_INV ? sym_k(N) : OP == SP_INVDIAG ? N
                          : OP == SP_GINV ? N * N : 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -833,13 +823,6 @@ static int launch_gen(const void *a, void *o, int64_t n, void *stream)
     return launch_redo<T, N, OP>(a, nullptr, o, n, p, stream);
 }
 
-// the orders whose N^2 record (+ temporaries) the backend holds in a lane without scratch (scripts/survey_spd.sh)
-template <typename T, int N, int OP>
-constexpr bool gen_fits()
-{
-    return sizeof(T) == 4 || N <= (OP == SP_GINV ? NFM_GEN_F64_MAX_INV : NFM_GEN_F64_MAX_DET);
-}
-
 template <typename T, int N, int OP>
 static int launch(const void *a, const void *b, void *o, int64_t n, const RowParams<T> &p, void *stream)
 {
@@ -868,10 +851,10 @@ static int call(int op, int64_t n, const void *a, const void *b, void *o, const 
     case SP_INVDIAG: return launch<T, N, SP_INVDIAG>(a, b, o, n, p, stream);
     case SP_DET: return launch<T, N, SP_DET>(a, b, o, n, p, stream);
     case SP_GINV:
-        if constexpr (gen_fits<T, N, SP_GINV>()) return launch_gen<T, N, SP_GINV>(a, o, n, stream);
+        if constexpr (gen_fits(sizeof(T) == 8, N, true)) return launch_gen<T, N, SP_GINV>(a, o, n, stream);
         else return NFM_EFALLBACK_RW;
     case SP_GDET:
-        if constexpr (gen_fits<T, N, SP_GDET>()) return launch_gen<T, N, SP_GDET>(a, o, n, stream);
+        if constexpr (gen_fits(sizeof(T) == 8, N, false)) return launch_gen<T, N, SP_GDET>(a, o, n, stream);
         else return NFM_EFALLBACK_RW;
     default: return NFM_EINVAL;
     }
@@ -965,14 +948,9 @@ int NFM_SPD_TNAME1(NFM_SPD_Q)(int M, int mode, int64_t n, const void *a, const v
 
 #if NFM_SPD_Q == 0
 // the front end lives in the q0 object of each dtype
-static bool spd_contig(const nfm_operand *o, int64_t rec, size_t elem)
-{
-    if (o == nullptr || o->ptr == nullptr) return false;
-    if (reinterpret_cast<uintptr_t>(o->ptr) % elem != 0) return false;
-    if (o->stride_inner != rec) return false;
-    if (rec > 1 && o->stride_col != 1) return false;
-    return true;
-}
+
+// compact records and vectors: one row of `rec` elements
+static bool spd_contig(const nfm_operand *o, int64_t rec) { return contiguous_records(o, rec, 1, rec, sizeof(TS)); }
 
 #if NFM_SPD_F64
 #define NFM_SPD_CALL(q) spd_call_f64_q##q
@@ -981,10 +959,6 @@ static bool spd_contig(const nfm_operand *o, int64_t rec, size_t elem)
 #endif
 static int spd_dispatch(int op, int M, int64_t n, const void *a, const void *b, void *o, const double *eps, void *stream)
 {
-    // measurement knob (only under NFM_DEBUG, like the row-wave ones): NFM_SPD_OFF=1 sends everything to the pivoted
-    // kernels, NFM_SPD_OFF=2 only the general matrices -- the A/B runs of scripts/bench_spd_ab.py
-    static const int off = [] { const char *e = roww::dbg_env("NFM_SPD_OFF"); return e ? atoi(e) : 0; }();
-    if (off == 1 || (off == 2 && (op == SP_GINV || op == SP_GDET))) return NFM_EFALLBACK_RW;
     switch ((M - 9) >> 1) {
     case 0: return NFM_SPD_CALL(0)(op, M, n, a, b, o, eps, stream);
     case 1: return NFM_SPD_CALL(1)(op, M, n, a, b, o, eps, stream);
@@ -999,8 +973,7 @@ int Spd<TS>::sym_solve(int M, int64_t ni, const nfm_operand *mat, const nfm_oper
                        const double *eps, void *stream)
 {
     const int K = M * (M + 1) / 2;
-    if (M < 9 || M > 16 || !spd_contig(mat, K, sizeof(TS)) || !spd_contig(vec, M, sizeof(TS)) ||
-        !spd_contig(out, M, sizeof(TS)))
+    if (M < 9 || M > 16 || !spd_contig(mat, K) || !spd_contig(vec, M) || !spd_contig(out, M))
         return NFM_EFALLBACK_RW;
     return spd_dispatch(SP_SOLVE, M, ni, mat->ptr, vec->ptr, out->ptr, eps, stream);
 }
@@ -1009,7 +982,7 @@ template <>
 int Spd<TS>::sym_invert(int M, int diag_only, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream)
 {
     const int K = M * (M + 1) / 2;
-    if (M < 9 || M > 16 || !spd_contig(mat, K, sizeof(TS)) || !spd_contig(out, diag_only ? M : K, sizeof(TS)))
+    if (M < 9 || M > 16 || !spd_contig(mat, K) || !spd_contig(out, diag_only ? M : K))
         return NFM_EFALLBACK_RW;
     return spd_dispatch(diag_only ? SP_INVDIAG : SP_INV, M, ni, mat->ptr, nullptr, out->ptr, nullptr, stream);
 }
@@ -1022,8 +995,6 @@ int Spd<TS>::sym_invert(int M, int diag_only, int64_t ni, const nfm_operand *mat
 static int spd_dispatch_strided(int op, int M, int64_t no, int64_t n, const nfm_operand *a, const nfm_operand *b,
                                 const nfm_operand *o, const double *eps, void *stream)
 {
-    static const int off = [] { const char *e = roww::dbg_env("NFM_SPD_OFF"); return e ? atoi(e) : 0; }();
-    if (off == 1 || off == 3) return NFM_EFALLBACK_RW; // (3: only the strided kernels off)
     if (M < 9 || M > 16 || a == nullptr || a->ptr == nullptr || o == nullptr || o->ptr == nullptr) return NFM_EFALLBACK_RW;
     switch ((M - 9) >> 1) {
     case 0: return NFM_SPD_SCALL(0)(op, M, no, n, a, b, o, eps, stream);
@@ -1048,11 +1019,10 @@ template <>
 int Spd<TS>::sym_matvec(int M, int mode, int64_t ni, const nfm_operand *mat, const nfm_operand *vec, const nfm_operand *inp,
                         const nfm_operand *out, void *stream)
 {
-    static const int off = [] { const char *e = roww::dbg_env("NFM_SPD_OFF"); return e ? atoi(e) : 0; }();
     const int K = M * (M + 1) / 2;
     // (13 and 14 measured level with their kernels of nfm_large.hip: 0.68-0.70 here, 0.72 there)
-    if (off == 1 || sizeof(TS) != 8 || M < 15 || M > 16 || !spd_contig(mat, K, sizeof(TS)) ||
-        !spd_contig(vec, M, sizeof(TS)) || !spd_contig(out, M, sizeof(TS)) || (mode != 0 && !spd_contig(inp, M, sizeof(TS))))
+    if (sizeof(TS) != 8 || M < 15 || M > 16 || !spd_contig(mat, K) || !spd_contig(vec, M) || !spd_contig(out, M) ||
+        (mode != 0 && !spd_contig(inp, M)))
         return NFM_EFALLBACK_RW;
     const void *c = mode != 0 ? inp->ptr : nullptr;
     switch ((M - 9) >> 1) {
@@ -1065,8 +1035,6 @@ template <>
 int Spd<TS>::sym_matvec_strided(int M, int mode, int64_t no, int64_t ni, const nfm_operand *mat, const nfm_operand *vec,
                                 const nfm_operand *inp, const nfm_operand *out, void *stream)
 {
-    static const int off = [] { const char *e = roww::dbg_env("NFM_SPD_OFF"); return e ? atoi(e) : 0; }();
-    if (off == 1 || off == 3) return NFM_EFALLBACK_RW;
     if (M < 9 || M > 16 || mat == nullptr || mat->ptr == nullptr || vec == nullptr || vec->ptr == nullptr ||
         out == nullptr || out->ptr == nullptr || (mode != 0 && (inp == nullptr || inp->ptr == nullptr)))
         return NFM_EFALLBACK_RW;
@@ -1104,8 +1072,9 @@ template <>
 int Spd<TS>::batch_inv(int Nn, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
 {
     const int64_t rec = (int64_t)Nn * Nn;
-    auto full = [&](const nfm_operand *o) { return spd_contig(o, rec, sizeof(TS)) && o->stride_row == Nn; };
-    if (Nn < 9 || Nn > 16 || !full(a) || !full(out)) return NFM_EFALLBACK_RW;
+    if (Nn < 9 || Nn > 16 || !contiguous_records(a, rec, Nn, Nn, sizeof(TS)) ||
+        !contiguous_records(out, rec, Nn, Nn, sizeof(TS)))
+        return NFM_EFALLBACK_RW;
     return spd_dispatch(SP_GINV, Nn, ni, a->ptr, nullptr, out->ptr, nullptr, stream);
 }
 
@@ -1113,7 +1082,7 @@ template <>
 int Spd<TS>::batch_det(int Nn, int64_t ni, const nfm_operand *a, const nfm_operand *out, void *stream)
 {
     const int64_t rec = (int64_t)Nn * Nn;
-    if (Nn < 9 || Nn > 16 || !spd_contig(a, rec, sizeof(TS)) || a->stride_row != Nn || out == nullptr ||
+    if (Nn < 9 || Nn > 16 || !contiguous_records(a, rec, Nn, Nn, sizeof(TS)) || out == nullptr ||
         out->ptr == nullptr || out->stride_inner != 1)
         return NFM_EFALLBACK_RW;
     return spd_dispatch(SP_GDET, Nn, ni, a->ptr, nullptr, out->ptr, nullptr, stream);
@@ -1123,7 +1092,7 @@ template <>
 int Spd<TS>::sym_det(int M, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream)
 {
     const int K = M * (M + 1) / 2;
-    if (M < 9 || M > 16 || !spd_contig(mat, K, sizeof(TS)) || out == nullptr || out->ptr == nullptr ||
+    if (M < 9 || M > 16 || !spd_contig(mat, K) || out == nullptr || out->ptr == nullptr ||
         out->stride_inner != 1)
         return NFM_EFALLBACK_RW;
     return spd_dispatch(SP_DET, M, ni, mat->ptr, nullptr, out->ptr, nullptr, stream);

@@ -9,6 +9,14 @@ namespace nfm {
 
 enum { SP_SOLVE = 0, SP_INV, SP_INVDIAG, SP_DET, SP_GINV, SP_GDET }; // G*: general (full, row-major) matrices
 
+// the orders of batchinv / batchdet whose N^2 record (+ temporaries) the backend holds in a lane without scratch
+// (scripts/survey_spd.sh): every float32 order, float64 up to 13 (N^2 doubles per lane + staging)
+constexpr int kGenF64MaxInv = 13, kGenF64MaxDet = 13;
+constexpr bool gen_fits(bool f64, int N, bool inv)
+{
+    return !f64 || N <= (inv ? kGenF64MaxInv : kGenF64MaxDet);
+}
+
 // one object per (dtype, pair of orders): part = dtype * 4 + q holds orders 9 + 2 q and 10 + 2 q
 #define NFM_SPD_DECL(S, Q)                                                                                                      \
     int spd_call_##S##_q##Q(int op, int M, int64_t n, const void *a, const void *b, void *o, const double *eps, void *stream); \

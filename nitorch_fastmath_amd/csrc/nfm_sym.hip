@@ -390,11 +390,11 @@ static int sym_solve_t(int M, int kind, int64_t no, int64_t ni, const nfm_operan
                 const int rc = Spd<T>::sym_solve(M, ni, mat, vec, out, p.has_eps ? p.eps : nullptr, stream);
                 if (rc != NFM_EFALLBACK) return rc;
             }
-            if (rowwave_first<T>(M, RWW_SOLVE)) { // one matrix per 16 lanes (nfm_rowwave.hip)
-                const int rc = RowWave<T>::sym_solve(M, ni, mat, vec, out, p.has_eps ? p.eps : nullptr, stream);
-                if (rc != NFM_EFALLBACK) return rc;
-            }
-            const int rc = Large<T>::sym_solve(M, ni, mat, vec, out, p.has_eps ? p.eps : nullptr, stream);
+            // pivoted: one matrix per 16 lanes where rowwave_choice names a form (nfm_rowwave.hip), else one per
+            // lane (nfm_large.hip)
+            const double *eps = p.has_eps ? p.eps : nullptr;
+            int rc = RowWave<T>::sym_solve(M, ni, mat, vec, out, eps, stream);
+            if (rc == NFM_EFALLBACK) rc = Large<T>::sym_solve(M, ni, mat, vec, out, eps, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
         if (kind == NFM_MAT_SYM && !pivoted) { // any strides, two batch levels: every lane addresses its own record (nfm_spd.hip)
@@ -476,12 +476,9 @@ static int sym_invert_t(int M, int flags, int64_t no, int64_t ni, const nfm_oper
             const int rc = Spd<T>::sym_invert(M, diag_only, ni, mat, out, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
-        if (no == 1 && rowwave_first<T>(M, diag_only ? RWW_INVDIAG_SYM : RWW_INV_SYM)) {
-            const int rc = RowWave<T>::sym_invert(M, diag_only, ni, mat, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
-        if (!diag_only && no == 1) {
-            const int rc = Large<T>::sym_invert(M, ni, mat, out, stream);
+        if (no == 1) { // pivoted: as sym_solve_t (the diagonal of the inverse has no lane-per-matrix form)
+            int rc = RowWave<T>::sym_invert(M, diag_only, ni, mat, out, stream);
+            if (rc == NFM_EFALLBACK && !diag_only) rc = Large<T>::sym_invert(M, ni, mat, out, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
         if (!pivoted) { // any strides, two batch levels (nfm_spd.hip)
@@ -503,22 +500,15 @@ template <typename T>
 static int sym_det_t(int M, int64_t no, int64_t ni, const nfm_operand *mat, const nfm_operand *out, void *stream)
 {
     if (M > 8) {
-        if (no == 1) { // positive definite first (nfm_spd.hip)
+        // positive definite first: contiguous records (nfm_spd.hip, every order of both dtypes; the groups that need
+        // a row exchange take the pivoted elimination there), then any strides and two batch levels (nfm_spd.hip),
+        // then the LDS-resident kernels
+        if (no == 1) {
             const int rc = Spd<T>::sym_det(M, ni, mat, out, stream);
             if (rc != NFM_EFALLBACK) return rc;
         }
-        if (no == 1 && rowwave_first<T>(M, RWW_DET_SYM)) {
-            const int rc = RowWave<T>::sym_det(M, ni, mat, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
-        if (no == 1) {
-            const int rc = Large<T>::sym_det(M, ni, mat, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
-        { // any strides, two batch levels (nfm_spd.hip)
-            const int rc = Spd<T>::sym_det_strided(M, no, ni, mat, out, stream);
-            if (rc != NFM_EFALLBACK) return rc;
-        }
+        const int rc = Spd<T>::sym_det_strided(M, no, ni, mat, out, stream);
+        if (rc != NFM_EFALLBACK) return rc;
         return big_sym_det<T>(M, no, ni, mat, out, stream);
     }
     NoParams p{0};

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""no-exchange-first kernels (nfm_spd.hip) against the pivoted kernels they stand in front of, same process
-arguments, one run per arm (NFM_DEBUG=1 NFM_SPD_OFF=1 is the pivoted arm): ms per call at several batch sizes."""
+"""no-exchange-first kernels (nfm_spd.hip) against the pivoted kernels they stand in front of (pivoting='always'),
+same arguments, both arms in one process: ms per call at several batch sizes.  batchinv / batchdet have no pivoted
+arm (their pivoted kernels of orders 9..16 only run for the matrices the no-exchange kernels hand them)."""
 import os
 import sys
 import torch
@@ -10,10 +11,8 @@ import nitorch_fastmath_amd as N  # noqa: E402
 from _timing import timeit  # noqa: E402
 
 dev = torch.device('cuda:0')
-arm = 'pivoted' if os.environ.get('NFM_SPD_OFF') else 'no-exchange first'
-print(f'# arm: {arm}')
-print('| op | batch | ms | GB/s | frac of 8 TB/s |')
-print('|---|---|---|---|---|')
+print('| op | arm | batch | ms | GB/s | frac of 8 TB/s |')
+print('|---|---|---|---|---|---|')
 # the compact symmetric functions: positive definite input (every matrix takes the unpivoted path), and the worst
 # case -- a batch in which EVERY matrix is indefinite (the attempt is wasted and every group is redone)
 for dtype, dn, sz in ((torch.float32, 'f32', 4), (torch.float64, 'f64', 8)):
@@ -28,13 +27,16 @@ for dtype, dn, sz in ((torch.float32, 'f32', 4), (torch.float64, 'f64', 8)):
                 mat[:, 0] = -2
             vec = torch.randn(n, M, device=dev, generator=g, dtype=dtype)
             out = torch.empty_like(vec)
-            t = timeit(lambda: N.sym_solve(mat, vec, out=out), 6)
-            b = (K + 2 * M) * sz
-            print(f'| sym_solve {M}x{M} {dn}, {what} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | {n * b / t / 8e12:.3f} |')
             inv = torch.empty_like(mat)
-            t = timeit(lambda: N.sym_invert(mat, out=inv), 6)
-            b = 2 * K * sz
-            print(f'| sym_invert {M}x{M} {dn}, {what} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | {n * b / t / 8e12:.3f} |')
+            for arm, piv in (('no-exchange first', 'auto'), ('pivoted', 'always')):
+                t = timeit(lambda: N.sym_solve(mat, vec, out=out, pivoting=piv), 6)
+                b = (K + 2 * M) * sz
+                print(f'| sym_solve {M}x{M} {dn}, {what} | {arm} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | '
+                      f'{n * b / t / 8e12:.3f} |')
+                t = timeit(lambda: N.sym_invert(mat, out=inv, pivoting=piv), 6)
+                b = 2 * K * sz
+                print(f'| sym_invert {M}x{M} {dn}, {what} | {arm} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | '
+                      f'{n * b / t / 8e12:.3f} |')
             del mat, vec, out, inv
 for dtype, dn, sz in ((torch.float32, 'f32', 4), (torch.float64, 'f64', 8)):
     for Nn in (9, 12, 16):
@@ -47,8 +49,10 @@ for dtype, dn, sz in ((torch.float32, 'f32', 4), (torch.float64, 'f64', 8)):
             a = torch.randn(n, Nn, Nn, device=dev, generator=g, dtype=dtype) + 8 * torch.eye(Nn, device=dev, dtype=dtype)
             t = timeit(lambda: N.batchdet(a), 6)
             b = (Nn * Nn + 1) * sz
-            print(f'| batchdet {Nn}x{Nn} {dn} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | {n * b / t / 8e12:.3f} |')
+            print(f'| batchdet {Nn}x{Nn} {dn} | no-exchange first | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | '
+                  f'{n * b / t / 8e12:.3f} |')
             t = timeit(lambda: N.batchinv(a), 6)
             b = 2 * Nn * Nn * sz
-            print(f'| batchinv {Nn}x{Nn} {dn} | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | {n * b / t / 8e12:.3f} |')
+            print(f'| batchinv {Nn}x{Nn} {dn} | no-exchange first | {n:.1e} | {t * 1e3:.3f} | {n * b / t / 1e9:.0f} | '
+                  f'{n * b / t / 8e12:.3f} |')
             del a

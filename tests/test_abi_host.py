@@ -2,6 +2,7 @@
 include/nfm_hip.h, argument validation answers without touching a GPU, and the
 host-side batch normalisation does what the kernels assume."""
 import ctypes
+import functools
 import os
 import re
 import numpy as np
@@ -233,13 +234,9 @@ def test_signatures_match_the_reference():
     assert names(N.reduce.nanstd) == ['input', 'dim', 'keepdim', 'unbiased', 'inplace', 'dtype', 'out']       # reduce.py:729-737
 
 
-def test_no_scratch_anywhere():
-    """Code-object facts (scripts/kernel_resources.py reads the `amdhsa.kernels` notes of the built
-    objects): NO kernel of the library has a private segment -- "one matrix per lane held entirely in
-    registers", and where a matrix does not fit a lane's 512 registers: float64 orders 13..16 of the
-    sym / batched ops take the one-matrix-per-16-lanes kernels of nfm_rowwave.hip, and the QR family at
-    orders 9..16 keeps its matrices in LDS ([element][lane] images, `qr_lds_kernel`) where they do not
-    fit (round 2 had 23 kernels with up to 11 KB of scratch per lane there)."""
+@functools.lru_cache(maxsize=None)
+def census():
+    """Every kernel of the built objects (scripts/kernel_resources.py reads their `amdhsa.kernels` notes)."""
     import glob
     import sys
     sys.path.insert(0, os.path.join(ROOT, 'scripts'))
@@ -250,7 +247,16 @@ def test_no_scratch_anywhere():
     objs = sorted(glob.glob(os.path.join(ROOT, 'nitorch_fastmath_amd', 'csrc', '*.o')))
     if not objs:
         pytest.skip('objects not built in this checkout (the .so alone travels to the GPU box)')
-    rows = KR.collect(objs)
+    return KR.collect(objs)
+
+
+def test_no_scratch_anywhere():
+    """Code-object facts: NO kernel of the library has a private segment -- "one matrix per lane held
+    entirely in registers", and where a matrix does not fit a lane's 512 registers: float64 orders 13..16
+    of the sym / batched ops take the one-matrix-per-16-lanes kernels of nfm_rowwave.hip, and the QR
+    family at orders 9..16 keeps its matrices in LDS ([element][lane] images, `qr_lds_kernel`) where they
+    do not fit (round 2 had 23 kernels with up to 11 KB of scratch per lane there)."""
+    rows = census()
     assert len(rows) > 1000
     bad = [(k['kernel'], k['scratch']) for k in rows if k['scratch']]
     assert not bad, bad[:5]
@@ -260,9 +266,26 @@ def test_no_scratch_anywhere():
     assert by['rec_kernel<float, SolveOp<float, 6, 0>, 1>']['vgpr'] <= 64
     assert by['rec_kernel<double, BatchInvOp<double, 8>, 1>']['vgpr'] <= 256       # 2 waves / SIMD
     rw = [k for k in rows if 'roww_kernel' in k['kernel']]
-    # (the 4-rows-per-lane float64 forms at orders 14..16 -- measurement forms, never the dispatch table's choice --
-    # park up to 30 values in accumulation registers: 262..286)
-    assert rw and max(k['vgpr'] for k in rw) <= 300 and not any(k['scratch'] for k in rw)
+    assert rw and max(k['vgpr'] for k in rw) <= 256 and not any(k['scratch'] for k in rw)  # >= 2 waves / SIMD
     # the positive-definite-first kernels (nfm_spd.hip): every (dtype, order, op)
     sp = [k for k in rows if 'spd_kernel' in k['kernel']]
     assert len(sp) == 2 * 8 * 4 and not any(k['scratch'] for k in sp)
+
+
+def test_only_reachable_kernel_forms_are_compiled():
+    """The library reads no environment (its dispatch is compile-time), and nfm_rowwave.hip compiles one
+    form per (dtype, order, op) -- the one rowwave_choice names -- and only for the cases the dispatch
+    reaches: pivoted sym_solve (float64 12..16), sym_invert (float64 10..16, float32 12..16), the diagonal
+    of the inverse (9..16, both dtypes), and float64 batchinv / batchdet 14..16."""
+    csrc = os.path.join(ROOT, 'nitorch_fastmath_amd', 'csrc')
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(('.hip', '.hpp', '.h', '.cpp')):
+            assert 'getenv' not in open(os.path.join(csrc, f)).read(), f
+    forms = {}
+    for k in census():
+        m = re.match(r'roww::roww_kernel<(float|double), (\d+), (\d+), \d, (?:true|false)>$', k['kernel'])
+        if m:
+            forms.setdefault(m.groups(), []).append(k['kernel'])
+    assert forms and all(len(v) == 1 for v in forms.values()), [v for v in forms.values() if len(v) > 1][:3]
+    n64 = sum(1 for t in forms if t[0] == 'double')
+    assert (n64, len(forms) - n64) == (26, 13), sorted(forms)
