@@ -165,6 +165,27 @@ int nfm_batch_matvec(int dtype, int rows, int cols, int64_t n_outer, int64_t n_i
                      const nfm_operand *a, const nfm_operand *v, const nfm_operand *out,
                      void *stream);
 
+/* ------------------------------------------------------------------ lie ---- */
+
+/* out = expm(x) for (D x D) matrices, `expm` / `expm_derivatives` without derivatives
+ * (`_impl/expm.py:15-49`, series `:139-190`).  Per matrix: scaling by 2^-s with ||x||_1 / 2^s <= 1,
+ * the reference's Taylor series up to the degree at which the bound of its term passes its own stop
+ * test (sum of squares <= D^2 tol, at most max_order terms), s squarings (quirk Q17); a matrix with a
+ * non-finite entry gives NaN everywhere (Q18).  D == 1 is exp().  float32 D = 1..8, float64 D = 1..7;
+ * NFM_ESIZE for every other order. */
+int nfm_lie_expm(int dtype, int D, int max_order, double tol, int64_t n_outer, int64_t n_inner,
+                 const nfm_operand *x, const nfm_operand *out, void *stream);
+
+/* Frechet derivatives of expm at x, the terms `dE` / `hE` of `expm_derivatives`
+ * (`_impl/expm.py:161-176`) for one direction (pair) per matrix:
+ *   b == NULL: out = L(x, a)      = d/dt expm(x + t a) at t = 0
+ *   else:      out = L2(x, a, b)  = d2/dt du expm(x + t a + u b) at 0 (symmetric in a and b)
+ * Same scaling, degree and squarings as nfm_lie_expm.  The adjoint L(x^T, g) is this call with x's
+ * stride_row and stride_col swapped.  D = 1..4, both dtypes; NFM_ESIZE otherwise. */
+int nfm_lie_expm_frechet(int dtype, int D, int max_order, double tol, int64_t n_outer, int64_t n_inner,
+                         const nfm_operand *x, const nfm_operand *a, const nfm_operand *b,
+                         const nfm_operand *out, void *stream);
+
 /* ------------------------------------------------------------ reductions ---- */
 
 #define NFM_RED_NANSUM 0 /* `nansum` reduce.py:471-510 : NaN -> 0              */

@@ -529,3 +529,24 @@ class SymMatmulFn(torch.autograd.Function):
         if gj is not None:
             gj = _sum_to(gj, j.shape).to(j.dtype)
         return gj, gh, None
+
+
+class ExpmFn(torch.autograd.Function):
+    """E = expm(M):  dM = L(M^T, G), the Frechet derivative at the transpose (one kernel launch:
+    M^T is M with its row and column strides swapped)."""
+
+    @staticmethod
+    def forward(ctx, m, max_order, tol):
+        from . import lie
+        with torch.no_grad():
+            e = lie._expm(m, max_order, tol)
+        ctx.save_for_backward(m)
+        ctx.limits = (max_order, tol)
+        return e
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import lie
+        (m,) = ctx.saved_tensors
+        return lie._frechet(m.transpose(-1, -2), g.to(m.dtype), None, *ctx.limits), None, None
