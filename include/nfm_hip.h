@@ -186,6 +186,26 @@ int nfm_lie_expm_frechet(int dtype, int D, int max_order, double tol, int64_t n_
                          const nfm_operand *x, const nfm_operand *a, const nfm_operand *b,
                          const nfm_operand *out, void *stream);
 
+/* out = logm(x), the principal logarithm of (D x D) matrices (`_impl/logm.py:102`, scipy on the CPU in the
+ * reference).  Per matrix: Denman-Beavers square roots until ||x - I||_1 <= 0.25, then 2^(s+1) atanh of
+ * (x - I)(x + I)^-1 by its series (quirk Q20).  Arithmetic and output in `dtype` (Q21).  A matrix with a
+ * non-finite entry, a singular one, or one with an eigenvalue on the closed negative real axis gives NaN
+ * everywhere (Q22); logm(I) is exactly 0.  D == 1 is log().  float32 D = 1..8, float64 D = 1..7; NFM_ESIZE
+ * for every other order. */
+int nfm_lie_logm(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *x,
+                 const nfm_operand *out, void *stream);
+
+/* out = logm(m^-1 a): one pivoted elimination on [m | a] in the lane, then the body of nfm_lie_logm -- the
+ * step of `meanm` (`lie.py:78-79`), with m at stride 0 along the set.  Same orders and NaN rule. */
+int nfm_lie_logm_solve(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *m,
+                       const nfm_operand *a, const nfm_operand *out, void *stream);
+
+/* out = L_log(x, g) = d/dt logm(x + t g) at t = 0: the steps of nfm_lie_logm differentiated.  The adjoint
+ * L_log(x^T, g) is this call with x's stride_row and stride_col swapped.  D = 1..5, both dtypes; NFM_ESIZE
+ * otherwise. */
+int nfm_lie_logm_frechet(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *x,
+                         const nfm_operand *g, const nfm_operand *out, void *stream);
+
 /* ------------------------------------------------------------ reductions ---- */
 
 #define NFM_RED_NANSUM 0 /* `nansum` reduce.py:471-510 : NaN -> 0              */

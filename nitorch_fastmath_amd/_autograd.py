@@ -550,3 +550,23 @@ class ExpmFn(torch.autograd.Function):
         from . import lie
         (m,) = ctx.saved_tensors
         return lie._frechet(m.transpose(-1, -2), g.to(m.dtype), None, *ctx.limits), None, None
+
+
+class LogmFn(torch.autograd.Function):
+    """L = logm(X):  dX = L_log(X^T, G), the Frechet derivative of the logarithm at the transpose (one kernel
+    launch: X^T is X with its row and column strides swapped)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        from . import logm
+        with torch.no_grad():
+            out = logm._logm(x)
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import logm
+        (x,) = ctx.saved_tensors
+        return logm._frechet(x.transpose(-1, -2), g.to(x.dtype))

@@ -49,6 +49,9 @@ SIGNATURES = {
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_lie_expm': [_i, _i, _i, ctypes.c_double, _i64, _i64, _op, _op, _vp],
     'nfm_lie_expm_frechet': [_i, _i, _i, ctypes.c_double, _i64, _i64, _op, _op, _op, _op, _vp],
+    'nfm_lie_logm': [_i, _i, _i64, _i64, _op, _op, _vp],
+    'nfm_lie_logm_solve': [_i, _i, _i64, _i64, _op, _op, _op, _vp],
+    'nfm_lie_logm_frechet': [_i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_reduce_all': [_i, _i, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp],
     'nfm_reduce_dim_workspace_bytes': [_i, _i, _i64, _i64, _i64, _i],
     'nfm_reduce_dim': [_i, _i, _i, _i64, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],

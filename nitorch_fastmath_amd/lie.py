@@ -12,7 +12,7 @@ derivatives the block identities
     L2(X, A, B) = expm([[X, A, B, 0], [0, X, 0, B], [0, 0, X, A], [0, 0, 0, X]])[:D, 3D:]
 
 `max_order` and `tol` do not apply on that route (matrix_exp picks its own degree).
-`logm` and `meanm` (scipy on the CPU in the reference) are not provided.
+`logm` and `meanm` are not names of this module: they live in `nitorch_fastmath_amd.logm`.
 """
 __all__ = ['expm', 'expm_derivatives']
 import ctypes
@@ -27,8 +27,8 @@ FRECHET_MAX = 4                                       # orders with a Frechet ke
 
 def __getattr__(name):
     if name in ('logm', 'meanm'):
-        raise AttributeError(f'nitorch_fastmath_amd.lie does not provide {name}: the reference computes it with '
-                             'scipy on the CPU; only expm and expm_derivatives run on the GPU here')
+        raise AttributeError(f'nitorch_fastmath_amd.lie does not provide {name}: import it from '
+                             f'nitorch_fastmath_amd.logm (`from nitorch_fastmath_amd.logm import {name}`)')
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 
