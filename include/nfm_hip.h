@@ -356,6 +356,39 @@ int nfm_qr_rq_hessenberg(int dtype, int N, int sym, int64_t n_outer, int64_t n_i
 int nfm_qr_eig_sym(int dtype, int N, int upper, int flags, int max_iter, double tol,
                    int64_t n_outer, int64_t n_inner, const nfm_operand *a, void *out, void *stream);
 
+/* ---------------------------------------------------------------- simplex ---- */
+
+/* softmax / log_softmax / logsumexp / logit along the middle axis of a contiguous (outer, K, inner)
+ * view, with the reference's implicit class (`simplex.py`), one voxel per lane.
+ * flags: NFM_SIMPLEX_IMPLICIT_IN   the input has a hidden class besides its K stored ones (logit 0; for
+ *                                  logit: probability 1 - sum, clamped at 1e-8); K' = K + 1 classes take
+ *                                  part in the arithmetic, the hidden one at position implicit_index;
+ *        NFM_SIMPLEX_IMPLICIT_OUT  the output does not store class implicit_index.
+ * 0 <= implicit_index < K'.  Without IMPLICIT_IN, logit takes class implicit_index as its reference.
+ * x: (outer, K, inner); out: (outer, K' - IMPLICIT_OUT, inner), at least one class; lse: (outer, inner), the
+ * per-voxel logsumexp -- the only output of NFM_SIMPLEX_LOGSUMEXP (out is ignored), optional second output
+ * of NFM_SIMPLEX_SOFTMAX, NULL otherwise.  K' = 1..17 runs with the classes in registers (K <= 16 with a hidden class, K <= 17 without), K up to
+ * NFM_SIMPLEX_MAX_K in sweeps over the class axis; NFM_ESIZE beyond.  NaN or +inf anywhere in a voxel makes
+ * its whole result NaN (as does a voxel of -inf without a hidden class). */
+#define NFM_SIMPLEX_SOFTMAX 0
+#define NFM_SIMPLEX_LOG_SOFTMAX 1
+#define NFM_SIMPLEX_LOGSUMEXP 2
+#define NFM_SIMPLEX_LOGIT 3
+#define NFM_SIMPLEX_SOFTMAX_BWD 4     /* saved = softmax output, grad_output like the output */
+#define NFM_SIMPLEX_LOGSUMEXP_BWD 5   /* saved = input, grad_output (outer, inner) */
+#define NFM_SIMPLEX_LOG_SOFTMAX_BWD 6 /* saved = input, grad_output like the output */
+#define NFM_SIMPLEX_IMPLICIT_IN 1
+#define NFM_SIMPLEX_IMPLICIT_OUT 2
+#define NFM_SIMPLEX_MAX_K 48
+int nfm_simplex_forward(int dtype, int op, int flags, int implicit_index, int64_t outer, int64_t K, int64_t inner,
+                        const void *x, void *out, void *lse, void *stream);
+
+/* Backward passes (op = NFM_SIMPLEX_*_BWD; flags, implicit_index, outer, K, inner as in the forward call):
+ * grad_input (outer, K, inner) from one saved tensor and grad_output.  A class the output dropped has no
+ * grad_output (it reads as 0); softmax rebuilds its probability as 1 - sum of the stored ones. */
+int nfm_simplex_backward(int dtype, int op, int flags, int implicit_index, int64_t outer, int64_t K, int64_t inner,
+                         const void *saved, const void *grad_output, void *grad_input, void *stream);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

@@ -8,7 +8,8 @@ sym_to_full, sym_outer, sym_matmul,
 batchmatvec / batchinv / batchdet, eig_sym (eigenvalues, and eigenvectors through Giles' formula,
 as upstream's `_EigSym` `_impl/qr.py:684-735` intends), sum / nansum / mean / nanmean,
 max / min / nanmax / nanmin (the cotangent goes to the selected element), var / std / nanvar /
-nanstd.  Everything else is forward-only and says so.
+nanstd, expm, logm, and the simplex functions softmax / log_softmax / logsumexp (one saved tensor each).
+Everything else is forward-only and says so.
 """
 import ctypes
 import torch
@@ -570,3 +571,94 @@ class LogmFn(torch.autograd.Function):
         from . import logm
         (x,) = ctx.saved_tensors
         return logm._frechet(x.transpose(-1, -2), g.to(x.dtype))
+
+
+class SoftmaxFn(torch.autograd.Function):
+    """p = softmax(x) along d with the implicit class at idx:  dx = p * (g - sum(g * p)) over the K' classes, one
+    backward kernel from the saved OUTPUT (a class the output dropped is rebuilt as 1 - sum, its g is 0; the
+    hidden class of an implicit input gets no gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, d, imp_in, imp_out, idx):
+        from . import simplex
+        with torch.no_grad():
+            p = simplex._forward(_lib.SX_SOFTMAX, x, d, imp_in, imp_out, idx)[0]
+        ctx.save_for_backward(p)
+        ctx.args = (d, x.shape[d], imp_in, imp_out, idx)
+        return p
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import simplex
+        (p,) = ctx.saved_tensors
+        return simplex._backward(_lib.SX_SOFTMAX_BWD, p, g, *ctx.args), None, None, None, None
+
+
+class LogsumexpFn(torch.autograd.Function):
+    """lse = logsumexp(x) along d (kept with size 1):  dx = softmax(x) * g, recomputed from the saved INPUT in one
+    backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, d, imp_in):
+        from . import simplex
+        K = x.shape[d]
+        idx = K if imp_in else 0
+        with torch.no_grad():
+            lse = simplex._forward(_lib.SX_LOGSUMEXP, x, d, imp_in, False, idx)[1]
+        ctx.save_for_backward(x)
+        ctx.args = (d, K, imp_in, False, idx)
+        return lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import simplex
+        (x,) = ctx.saved_tensors
+        return simplex._backward(_lib.SX_LOGSUMEXP_BWD, x, g, *ctx.args), None, None
+
+
+class LogSoftmaxFn(torch.autograd.Function):
+    """y = log_softmax(x):  dx = g - softmax(x) * sum(g) over the K' classes, from the saved INPUT (the output
+    may lack a class, the input never lacks information)."""
+
+    @staticmethod
+    def forward(ctx, x, d, imp_in, imp_out, idx):
+        from . import simplex
+        with torch.no_grad():
+            y = simplex._forward(_lib.SX_LOG_SOFTMAX, x, d, imp_in, imp_out, idx)[0]
+        ctx.save_for_backward(x)
+        ctx.args = (d, x.shape[d], imp_in, imp_out, idx)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import simplex
+        (x,) = ctx.saved_tensors
+        return simplex._backward(_lib.SX_LOG_SOFTMAX_BWD, x, g, *ctx.args), None, None, None, None
+
+
+class LogitFn(torch.autograd.Function):
+    """y = logit(p): forward kernel; the gradient is torch's, through the composition `simplex._torch_logit` rebuilt
+    on the saved INPUT (three elementwise ops and a sum: no kernel of its own)."""
+
+    @staticmethod
+    def forward(ctx, x, d, imp_in, imp_out, idx):
+        from . import simplex
+        with torch.no_grad():
+            y = simplex._forward(_lib.SX_LOGIT, x, d, imp_in, imp_out, idx)[0]
+        ctx.save_for_backward(x)
+        ctx.args = (d, imp_in, imp_out, idx)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import simplex
+        (x,) = ctx.saved_tensors
+        with torch.enable_grad():
+            xi = x.detach().requires_grad_()
+            y = simplex._torch_logit(xi, *ctx.args)[0]
+            (gx,) = torch.autograd.grad(y, xi, g.to(x.dtype))
+        return gx, None, None, None, None

@@ -18,6 +18,9 @@ EIG_VECTORS, EIG_FAST = 1, 2                 # flags of nfm_qr_eig_sym
 MAT_PIVOTED, INVERT_PIVOTED = 16, 2          # include/nfm_hip.h: NFM_MAT_PIVOTED, NFM_INVERT_PIVOTED
 RED_NANSUM, RED_NANMAX, RED_NANMIN, RED_SUM, RED_MAX, RED_MIN, RED_NANCOUNT, RED_NANSUMSQ = range(8)
 MAX_DIM = 16
+# include/nfm_hip.h: NFM_SIMPLEX_*
+SX_SOFTMAX, SX_LOG_SOFTMAX, SX_LOGSUMEXP, SX_LOGIT, SX_SOFTMAX_BWD, SX_LOGSUMEXP_BWD, SX_LOG_SOFTMAX_BWD = range(7)
+SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
 SIDE = {'left': 0, 'right': 1, 'both': 2}
 
 
@@ -52,6 +55,8 @@ SIGNATURES = {
     'nfm_lie_logm': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_lie_logm_solve': [_i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_lie_logm_frechet': [_i, _i, _i64, _i64, _op, _op, _op, _vp],
+    'nfm_simplex_forward': [_i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_simplex_backward': [_i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'nfm_reduce_all': [_i, _i, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp],
     'nfm_reduce_dim_workspace_bytes': [_i, _i, _i64, _i64, _i64, _i],
     'nfm_reduce_dim': [_i, _i, _i, _i64, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],
