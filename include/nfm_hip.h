@@ -389,6 +389,48 @@ int nfm_simplex_forward(int dtype, int op, int flags, int implicit_index, int64_
 int nfm_simplex_backward(int dtype, int op, int flags, int implicit_index, int64_t outer, int64_t K, int64_t inner,
                          const void *saved, const void *grad_output, void *grad_input, void *stream);
 
+/* ---------------------------------------------------------------- special ---- */
+
+/* Special functions of `special.py` over a flat range of n elements (float32 / float64), one 16-byte vector
+ * per lane, any element-aligned pointers.  Return codes: NFM_EDTYPE unknown dtype; NFM_EINVAL mode outside
+ * 0..2, nu < 0 or not finite, N < 0, K < 0, order < 1, n < 0, a null pointer with n > 0; NFM_ESIZE
+ * N > NFM_SPECIAL_MAX_N; NFM_EALIGN a pointer not aligned to its element size; n == 0 succeeds with null
+ * pointers.  The output of a forward call may be its input (in place).
+ *
+ * besseli: the modified Bessel function of the first kind I_nu(z), z >= 0.  mode 0: I_nu(z); 1: I_nu(z)
+ * exp(-z); 2: log I_nu(z).  nu == 0 and nu == 1 run the reference's polynomials (A&S 9.8.1-9.8.4, 5e-7 from
+ * the function); any other nu >= 0 is the function itself (series / uniform asymptotic expansion in double).
+ * z = 0: 1 / 1 / 0 at nu = 0, 0 / 0 / -inf above; z = +inf: +inf / 0 / +inf; NaN -> NaN; z < 0 at another nu
+ * than 0 or 1 -> NaN. */
+#define NFM_SPECIAL_MAX_N 8
+int nfm_special_besseli(int dtype, int mode, double nu, int64_t n, const void *z, void *out, void *stream);
+/* grad_z = grad_out * d(out)/dz from z and the saved output: with r = I_{nu+1}(z) / I_nu(z),
+ * d log I = r + nu/z, dI = I (r + nu/z), d(I exp(-z)) = I exp(-z) (r + nu/z - 1); the limit at z = 0. */
+int nfm_special_besseli_backward(int dtype, int mode, double nu, int64_t n, const void *z, const void *out,
+                                 const void *grad_out, void *grad_z, void *stream);
+/* I_{nu+1}(x) / I_nu(x) by Amos (1974): eq. 20a at order nu + K, N rounds of eq. 20b (N <= NFM_SPECIAL_MAX_N),
+ * K steps of the backward recurrence; 0 at x = 0 and 1 at x = +inf. */
+int nfm_special_besseli_ratio(int dtype, double nu, int N, int K, int64_t n, const void *x, void *out, void *stream);
+/* grad_x = grad_out * (1 - r^2 - (2 nu + 1) r / x) on the saved output r (1 / (2 nu + 2) at x = 0). */
+int nfm_special_besseli_ratio_backward(int dtype, double nu, int64_t n, const void *x, const void *out,
+                                       const void *grad_out, void *grad_x, void *stream);
+/* sum_{p=1..order} digamma(x + (1 - p) / 2); digamma(0) = -inf, NaN at the negative integers. */
+int nfm_special_mvdigamma(int dtype, int order, int64_t n, const void *x, void *out, void *stream);
+/* grad_x = grad_out * sum_p trigamma(x + (1 - p) / 2). */
+int nfm_special_mvdigamma_backward(int dtype, int order, int64_t n, const void *x, const void *grad_out, void *grad_x,
+                                   void *stream);
+/* The same arithmetic on the CPU with host pointers and no GPU: what a host test can check numerically.
+ * func: NFM_SPECIAL_*; mode_or_order: mode of besseli, order of mvdigamma; unused arguments are ignored
+ * (saved_out / grad_out may be NULL for the forward functions). */
+#define NFM_SPECIAL_BESSELI 0
+#define NFM_SPECIAL_BESSELI_BWD 1
+#define NFM_SPECIAL_RATIO 2
+#define NFM_SPECIAL_RATIO_BWD 3
+#define NFM_SPECIAL_MVDIGAMMA 4
+#define NFM_SPECIAL_MVDIGAMMA_BWD 5
+int nfm_special_host_eval(int func, int dtype, int mode_or_order, double nu, int N, int K, int64_t n, const void *x,
+                          const void *saved_out, const void *grad_out, void *result);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

@@ -8,7 +8,8 @@ sym_to_full, sym_outer, sym_matmul,
 batchmatvec / batchinv / batchdet, eig_sym (eigenvalues, and eigenvectors through Giles' formula,
 as upstream's `_EigSym` `_impl/qr.py:684-735` intends), sum / nansum / mean / nanmean,
 max / min / nanmax / nanmin (the cotangent goes to the selected element), var / std / nanvar /
-nanstd, expm, logm, and the simplex functions softmax / log_softmax / logsumexp (one saved tensor each).
+nanstd, expm, logm, the simplex functions softmax / log_softmax / logsumexp (one saved tensor each) and the special
+functions besseli / besseli_ratio / mvdigamma.
 Everything else is forward-only and says so.
 """
 import ctypes
@@ -662,3 +663,65 @@ class LogitFn(torch.autograd.Function):
             y = simplex._torch_logit(xi, *ctx.args)[0]
             (gx,) = torch.autograd.grad(y, xi, g.to(x.dtype))
         return gx, None, None, None, None
+
+
+class BesseliFn(torch.autograd.Function):
+    """y = besseli(nu, z) in mode `code`:  with r = I_{nu+1}(z) / I_nu(z), d log I = r + nu/z, dI = I (r + nu/z),
+    d(I exp(-z)) = I exp(-z) (r + nu/z - 1); one backward kernel from z and the saved output."""
+
+    @staticmethod
+    def forward(ctx, z, nu, code):
+        from . import special
+        with torch.no_grad():
+            y = special._besseli_forward(nu, z, code)
+        ctx.save_for_backward(z, y)
+        ctx.args = (nu, code)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import special
+        z, y = ctx.saved_tensors
+        nu, code = ctx.args
+        return special._besseli_backward(nu, z, y, g, code), None, None
+
+
+class BesseliRatioFn(torch.autograd.Function):
+    """r = besseli_ratio(nu, x):  dr = 1 - r^2 - (2 nu + 1) r / x (Riccati) on the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, nu, N, K):
+        from . import special
+        with torch.no_grad():
+            r = special._ratio_forward(nu, x, N, K)
+        ctx.save_for_backward(x, r)
+        ctx.nu = nu
+        return r
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import special
+        x, r = ctx.saved_tensors
+        return special._ratio_backward(ctx.nu, x, r, g), None, None, None
+
+
+class MvDigammaFn(torch.autograd.Function):
+    """y = mvdigamma(x, order):  dx = g * sum_p trigamma(x + (1 - p) / 2), one backward kernel from the saved input."""
+
+    @staticmethod
+    def forward(ctx, x, order):
+        from . import special
+        with torch.no_grad():
+            y = special._digamma_forward(x, order)
+        ctx.save_for_backward(x)
+        ctx.order = order
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import special
+        (x,) = ctx.saved_tensors
+        return special._digamma_backward(x, g, ctx.order), None

@@ -21,6 +21,9 @@ MAX_DIM = 16
 # include/nfm_hip.h: NFM_SIMPLEX_*
 SX_SOFTMAX, SX_LOG_SOFTMAX, SX_LOGSUMEXP, SX_LOGIT, SX_SOFTMAX_BWD, SX_LOGSUMEXP_BWD, SX_LOG_SOFTMAX_BWD = range(7)
 SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
+# include/nfm_hip.h: NFM_SPECIAL_*
+SP_BESSELI, SP_BESSELI_BWD, SP_RATIO, SP_RATIO_BWD, SP_MVDIGAMMA, SP_MVDIGAMMA_BWD = range(6)
+SP_MAX_N = 8
 SIDE = {'left': 0, 'right': 1, 'both': 2}
 
 
@@ -57,6 +60,13 @@ SIGNATURES = {
     'nfm_lie_logm_frechet': [_i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_simplex_forward': [_i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
     'nfm_simplex_backward': [_i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_special_besseli': [_i, _i, ctypes.c_double, _i64, _vp, _vp, _vp],
+    'nfm_special_besseli_backward': [_i, _i, ctypes.c_double, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_special_besseli_ratio': [_i, ctypes.c_double, _i, _i, _i64, _vp, _vp, _vp],
+    'nfm_special_besseli_ratio_backward': [_i, ctypes.c_double, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_special_mvdigamma': [_i, _i, _i64, _vp, _vp, _vp],
+    'nfm_special_mvdigamma_backward': [_i, _i, _i64, _vp, _vp, _vp, _vp],
+    'nfm_special_host_eval': [_i, _i, _i, ctypes.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_reduce_all': [_i, _i, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp],
     'nfm_reduce_dim_workspace_bytes': [_i, _i, _i64, _i64, _i64, _i],
     'nfm_reduce_dim': [_i, _i, _i, _i64, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],
