@@ -12,15 +12,10 @@ nanstd, expm, logm, the simplex functions softmax / log_softmax / logsumexp (one
 functions besseli / besseli_ratio / mvdigamma.
 Everything else is forward-only and says so.
 """
-import ctypes
 import torch
 from torch.autograd.function import once_differentiable
 from . import _lib
-from ._dispatch import on_device, Batch, dtype_code, expand_batch, stream_ptr, broadcast_shapes
-
-
-def needs_grad(*tensors):
-    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+from ._dispatch import Batch, expand_batch, broadcast_shapes, launch
 
 
 def _sum_to(g, shape):
@@ -37,11 +32,7 @@ def sym_outer2(x, y, neg=False):
     batch = broadcast_shapes(x.shape[:-1], y.shape[:-1])
     out = torch.empty(tuple(batch) + (M * (M + 1) // 2,), dtype=dtype, device=dev)
     b = Batch(batch, [expand_batch(batch, x, 1), expand_batch(batch, y, 1), out], [1, 1, 1])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_outer2(dtype_code(dtype), M, int(neg), b.n_outer, b.n_inner,
-                                             ctypes.byref(o[0]), ctypes.byref(o[1]), ctypes.byref(o[2]),
-                                             stream_ptr(dev)))
+    launch(_lib.lib().nfm_sym_outer2, dev, dtype, (M, int(neg)), b)
     return out
 
 

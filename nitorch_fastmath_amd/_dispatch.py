@@ -1,6 +1,8 @@
 """Host-side plumbing between torch tensors and the C ABI: dtype codes, stream,
 broadcast normalisation and the two-level batch collapse (no data movement unless
-the broadcast batch genuinely needs more than two stride levels)."""
+the broadcast batch genuinely needs more than two stride levels), and the one way into
+the library: `prepare` checks the operands, `launch` / `call` run an entry point."""
+from ctypes import byref
 import torch
 from . import _lib
 
@@ -29,6 +31,10 @@ def require_gpu(*tensors):
         elif t.device != dev:
             raise RuntimeError(f'all tensors must be on the same device ({dev} vs {t.device})')
     return dev
+
+
+def needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
 
 
 def no_grad_required(*tensors):
@@ -110,6 +116,40 @@ def common_dtype(dtype, *tensors):
             continue
         out = t.dtype if out is None else torch.promote_types(out, t.dtype)
     return out
+
+
+def prepare(dtype, *tensors, grad_ok=False):
+    """The operand check of every facade function: tensors (None = an absent optional operand) on one GPU,
+    forward-only unless `grad_ok`, float32 / float64.  Returns (device, dtype, tensors cast to dtype);
+    `dtype=None` takes the promoted dtype of the operands."""
+    tensors = [None if t is None else torch.as_tensor(t) for t in tensors]
+    dev = require_gpu(*tensors)
+    if not grad_ok:
+        no_grad_required(*tensors)
+    dtype = common_dtype(dtype, *tensors)
+    dtype_code(dtype)
+    return dev, dtype, same_dtype(tensors, dtype)
+
+
+def call(fn, dev, *args):
+    """Run the C-ABI entry point `fn(*args, stream)` on torch's current stream of `dev`; a status other
+    than 0 raises (`_lib.check`)."""
+    with on_device(dev):
+        _lib.check(fn(*args, stream_ptr(dev)))
+
+
+def launch(fn, dev, dtype, scalars, b, slots=None, tail=()):
+    """Run an operand entry point on the Batch `b`:
+    `fn(dtype code, *scalars, n_outer, n_inner, *operands, *tail, stream)`, then `b.finish()`.
+    `slots` lists, in the order of the C arguments, the index in `b.operands` of each operand argument
+    (None = a NULL pointer for an optional operand that is absent); the default is every operand of `b`
+    in its order.  `tail` holds the non-operand arguments before the stream (an eps array, a raw pointer)."""
+    o = b.operands
+    refs = [byref(x) for x in o] if slots is None else [None if k is None else byref(o[k]) for k in slots]
+    with on_device(dev):     # (`call`, written out: small batches are launch-bound and a frame is 0.1 us)
+        _lib.check(fn(_DTYPES[dtype], *scalars, b.n_outer, b.n_inner, *refs, *tail, stream_ptr(dev)))
+    if b._copyback is not None:
+        b.finish()
 
 
 def _collapse(shape, strides_list):

@@ -9,20 +9,9 @@ lane-per-matrix HIP kernel: adjugate closed forms up to 3x3, in-register
 Gauss-Jordan / LU with partial pivoting up to 8x8, LDS-resident LU up to 16x16.
 """
 __all__ = ['batchmatvec', 'batchdet', 'batchinv']
-import ctypes
 import torch
 from . import _lib
-from ._dispatch import (same_dtype, on_device, Batch, broadcast_shapes, common_dtype, dtype_code, expand_batch, no_grad_required,
-                        require_gpu, stream_ptr)
-
-
-def _prep(*tensors):
-    tensors = [torch.as_tensor(t) for t in tensors]
-    dev = require_gpu(*tensors)
-    no_grad_required(*tensors)
-    dtype = common_dtype(None, *tensors)
-    dtype_code(dtype)
-    return dev, dtype, same_dtype(tensors, dtype)
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
 
 
 def _like_or_contiguous(like, shape, dtype, dev):
@@ -41,10 +30,10 @@ def batchdet(a):
 
     a : `(..., n, n) tensor` -> `(...) tensor`.  Replaces `_impl/batched.py:35-63`.
     """
-    from ._autograd import BatchDetFn, needs_grad
+    from ._autograd import BatchDetFn
     if needs_grad(a):
         return BatchDetFn.apply(torch.as_tensor(a))
-    dev, dtype, (a,) = _prep(a)
+    dev, dtype, (a,) = prepare(None, a)
     n = a.shape[-1]
     assert a.shape[-2] == n, 'Expected square matrices'
     if n > _lib.MAX_DIM:          # the reference's own route for every order (`_impl/batched.py:53-54`), on the device
@@ -52,11 +41,7 @@ def batchdet(a):
     batch = a.shape[:-2]
     out = torch.empty(batch, dtype=dtype, device=dev)
     b = Batch(batch, [a, out], [2, 0], pack=n > 8)
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_batch_det(dtype_code(dtype), n, b.n_outer, b.n_inner,
-                                            ctypes.byref(o[0]), ctypes.byref(o[1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_batch_det, dev, dtype, (n,), b)
     return out
 
 
@@ -70,10 +55,10 @@ def batchinv(a, perturb=False):
         determinant perturbation `(max|a| - min|a|) * 1e-12` (`_impl/batched.py:74-76`).
         The default matches the reference's CPU path (`a.inverse()`).
     """
-    from ._autograd import BatchInvFn, needs_grad
+    from ._autograd import BatchInvFn
     if needs_grad(a):
         return BatchInvFn.apply(torch.as_tensor(a), bool(perturb))
-    dev, dtype, (a,) = _prep(a)
+    dev, dtype, (a,) = prepare(None, a)
     n = a.shape[-1]
     assert a.shape[-2] == n, 'Expected square matrices'
     if n > _lib.MAX_DIM:          # `a.inverse()` (`_impl/batched.py:119-120`), on the device
@@ -81,12 +66,7 @@ def batchinv(a, perturb=False):
     batch = a.shape[:-2]
     out = _like_or_contiguous(a if n <= 8 else None, tuple(batch) + (n, n), dtype, dev)
     b = Batch(batch, [a, out], [2, 2], pack=n > 8)
-    o = b.operands
-    flags = _lib.FLAG_TS_PERTURB if perturb else 0
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_batch_inv(dtype_code(dtype), n, flags, b.n_outer, b.n_inner,
-                                            ctypes.byref(o[0]), ctypes.byref(o[1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_batch_inv, dev, dtype, (n, _lib.FLAG_TS_PERTURB if perturb else 0), b)
     return out
 
 
@@ -95,20 +75,15 @@ def batchmatvec(mat, vec):
 
     mat : `(..., m, n)`, vec : `(..., n)` -> `(..., m)`.  Replaces `_impl/batched.py:154-190`.
     """
-    from ._autograd import BatchMatvecFn, needs_grad
+    from ._autograd import BatchMatvecFn
     if needs_grad(mat, vec):
         return BatchMatvecFn.apply(torch.as_tensor(mat), torch.as_tensor(vec))
-    dev, dtype, (mat, vec) = _prep(mat, vec)
+    dev, dtype, (mat, vec) = prepare(None, mat, vec)
     m, n = mat.shape[-2:]
     if vec.shape[-1] != n:
         raise ValueError(f'matrix {tuple(mat.shape[-2:])} and vector ({vec.shape[-1]},) do not match')
     batch = broadcast_shapes(mat.shape[:-2], vec.shape[:-1])
     out = _like_or_contiguous(vec if m == n else None, tuple(batch) + (m,), dtype, dev)
     b = Batch(batch, [expand_batch(batch, mat, 2), expand_batch(batch, vec, 1), out], [2, 1, 1])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_batch_matvec(dtype_code(dtype), m, n, b.n_outer, b.n_inner,
-                                               ctypes.byref(o[0]), ctypes.byref(o[1]),
-                                               ctypes.byref(o[2]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_batch_matvec, dev, dtype, (m, n), b)
     return out

@@ -9,25 +9,6 @@
 
 namespace nfm {
 
-#define NFM_CASE_N(Nv, ...)   \
-    case Nv: {                \
-        constexpr int N = Nv; \
-        __VA_ARGS__;          \
-    } break;
-#define NFM_SWITCH_N8(Nexpr, ...)  \
-    switch (Nexpr) {               \
-        NFM_CASE_N(1, __VA_ARGS__) \
-        NFM_CASE_N(2, __VA_ARGS__) \
-        NFM_CASE_N(3, __VA_ARGS__) \
-        NFM_CASE_N(4, __VA_ARGS__) \
-        NFM_CASE_N(5, __VA_ARGS__) \
-        NFM_CASE_N(6, __VA_ARGS__) \
-        NFM_CASE_N(7, __VA_ARGS__) \
-        NFM_CASE_N(8, __VA_ARGS__) \
-    default:                       \
-        return NFM_ESIZE;          \
-    }
-
 // Orders 9..16: contiguous row-major matrices go to the diagonal-pivots-first kernels of nfm_spd.hip (float32
 // 9..16, float64 9..13: gen_fits), which hand the wavefronts that need a row exchange to the pivoted elimination;
 // float64 14..16 do not fit a lane there and take one matrix per 16 lanes (nfm_rowwave.hip).  Any other layout:
@@ -45,8 +26,9 @@ static int batch_inv_t(int N, int flags, int64_t no, int64_t ni, const nfm_opera
         return big_batch_inv<T>(N, no, ni, a, out, stream);
     }
     InvParams p{(flags & NFM_FLAG_TS_PERTURB) ? 1 : 0};
-    NFM_SWITCH_N8(N, return (rec_launch<T, BatchInvOp<T, N>>(a, nullptr, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(N, NFM_ESIZE, [&](auto n) {
+        return rec_launch<T, BatchInvOp<T, n()>>(a, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 // orders 9..16: as batch_inv_t
@@ -62,8 +44,9 @@ static int batch_det_t(int N, int64_t no, int64_t ni, const nfm_operand *a, cons
         return big_batch_det<T>(N, no, ni, a, out, stream);
     }
     NoParamsB p{0};
-    NFM_SWITCH_N8(N, return (rec_launch<T, BatchDetOp<T, N>>(a, nullptr, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(N, NFM_ESIZE, [&](auto n) {
+        return rec_launch<T, BatchDetOp<T, n()>>(a, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T>
@@ -88,41 +71,34 @@ extern "C" {
 int nfm_batch_inv(int dtype, int N, int flags, int64_t n_outer, int64_t n_inner, const nfm_operand *a,
                   const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
     if (rc) return rc;
-    if (N < 1 || N > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? batch_inv_t<float>(N, flags, n_outer, n_inner, a, out, stream)
-                            : batch_inv_t<double>(N, flags, n_outer, n_inner, a, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return batch_inv_t<decltype(t)>(N, flags, n_outer, n_inner, a, out, stream);
+    });
 }
 
 int nfm_batch_det(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *a, const nfm_operand *out,
                   void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
     if (rc) return rc;
-    if (N < 1 || N > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? batch_det_t<float>(N, n_outer, n_inner, a, out, stream)
-                            : batch_det_t<double>(N, n_outer, n_inner, a, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return batch_det_t<decltype(t)>(N, n_outer, n_inner, a, out, stream);
+    });
 }
 
 int nfm_batch_matvec(int dtype, int rows, int cols, int64_t n_outer, int64_t n_inner, const nfm_operand *a,
                      const nfm_operand *v, const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {rows, cols});
     if (rc) return rc;
-    if (rows < 1 || rows > NFM_MAX_DIM || cols < 1 || cols > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(v, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? batch_matvec_t<float>(rows, cols, n_outer, n_inner, a, v, out, stream)
-                            : batch_matvec_t<double>(rows, cols, n_outer, n_inner, a, v, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a, v, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return batch_matvec_t<decltype(t)>(rows, cols, n_outer, n_inner, a, v, out, stream);
+    });
 }
 
 } // extern "C"

@@ -20,6 +20,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <atomic>
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
 #include "../../include/nfm_hip.h"
 
 namespace nfm {
@@ -498,6 +501,61 @@ inline int check_operand(const nfm_operand *op, int dtype, bool nonempty)
     const size_t e = dtype == NFM_F32 ? 4 : 8;
     if (reinterpret_cast<uintptr_t>(op->ptr) % e != 0) return NFM_EALIGN;
     return NFM_OK;
+}
+
+// ---- the prologue of an entry point with nfm_operand arguments, in two calls around the entry point's
+// own flag / kind checks: check_batch, [own checks], check_operands.  The precedence of the codes is part
+// of the ABI (tests/test_abi_host.py pins it): dtype, negative counts, n_outer, orders, own checks, then
+// the operands in argument order (null, null pointer with a non-empty batch, alignment).
+inline int check_batch(int dtype, int64_t n_outer, int64_t n_inner, std::initializer_list<int> orders,
+                       int max_order = NFM_MAX_DIM)
+{
+    const int rc = check_common(dtype, n_outer, n_inner);
+    if (rc) return rc;
+    for (int m : orders)
+        if (m < 1 || m > max_order) return NFM_ESIZE;
+    return NFM_OK;
+}
+
+// an operand of the list; `required = false` marks one that this call does not read (it is not checked)
+struct OperandArg {
+    const nfm_operand *op;
+    bool required;
+    OperandArg(const nfm_operand *o, bool req = true) : op(o), required(req) {}
+};
+
+inline int check_operands(int dtype, int64_t n_outer, int64_t n_inner, std::initializer_list<OperandArg> ops)
+{
+    const bool nonempty = n_outer > 0 && n_inner > 0;
+    for (const OperandArg &a : ops) {
+        const int rc = a.required ? check_operand(a.op, dtype, nonempty) : NFM_OK;
+        if (rc) return rc;
+    }
+    return NFM_OK;
+}
+
+// f(float{}) or f(double{}) by the (already checked) dtype code: `[&](auto t) { using T = decltype(t); ... }`
+template <typename F>
+inline int by_dtype(int dtype, F &&f)
+{
+    return dtype == NFM_F32 ? f(float{}) : f(double{});
+}
+
+// The order as a compile-time constant: f(std::integral_constant<int, m>{}) for the m in 1..MAX that equals
+// `order`, and `miss` when there is none (use `[&](auto m) { constexpr int M = m; ... }`).  Only 1..MAX are
+// instantiated: a per-dtype limit below MAX stays an `if constexpr` inside f.
+template <typename F, int... I>
+inline int switch_order_seq(int order, int miss, F &f, std::integer_sequence<int, I...>)
+{
+    int rc = miss;
+    (void)((order == I + 1 && ((rc = f(std::integral_constant<int, I + 1>{})), true)) || ...);
+    return rc;
+}
+
+template <int MAX, typename F>
+inline int switch_order(int order, int miss, F &&f)
+{
+    return switch_order_seq(order, miss, f, std::make_integer_sequence<int, MAX>{});
 }
 
 inline int launch_status()

@@ -36,14 +36,8 @@ template <typename T>
 static int logm_t(int D, const nfm_operand *m, const nfm_operand *a, const nfm_operand *out, int64_t no,
                   int64_t ni, void *stream)
 {
-#define NFM_LOGM(Dv) \
-    case Dv: return logm_one<T, Dv>(m, a, out, no, ni, stream);
-    switch (D) {
-        NFM_LOGM(1) NFM_LOGM(2) NFM_LOGM(3) NFM_LOGM(4) NFM_LOGM(5) NFM_LOGM(6) NFM_LOGM(7) NFM_LOGM(8)
-    default: break;
-    }
-#undef NFM_LOGM
-    return NFM_ESIZE;
+    static_assert(NFM_LOGM_MAX_F32 >= NFM_LOGM_MAX_F64, "the switch runs to the larger of the two limits");
+    return switch_order<NFM_LOGM_MAX_F32>(D, NFM_ESIZE, [&](auto d) { return logm_one<T, d()>(m, a, out, no, ni, stream); });
 }
 
 template <typename T>
@@ -51,23 +45,9 @@ static int logm_frechet_t(int D, const nfm_operand *x, const nfm_operand *g, con
                           int64_t ni, void *stream)
 {
     const LogmParams p{};
-#define NFM_LOGMF(Dv) \
-    case Dv: return rec_launch<T, LogmFrechetOp<T, Dv>>(x, g, nullptr, out, no, ni, p, stream);
-    switch (D) {
-        NFM_LOGMF(1) NFM_LOGMF(2) NFM_LOGMF(3) NFM_LOGMF(4) NFM_LOGMF(5)
-    default: break;
-    }
-#undef NFM_LOGMF
-    static_assert(NFM_LOGM_FRECHET_MAX == 5, "the switch above lists the orders");
-    return NFM_ESIZE;
-}
-
-static int logm_check(int dtype, int D, int64_t no, int64_t ni)
-{
-    int rc = check_common(dtype, no, ni);
-    if (rc) return rc;
-    if (D < 1 || D > NFM_MAX_DIM) return NFM_ESIZE;
-    return NFM_OK;
+    return switch_order<NFM_LOGM_FRECHET_MAX>(D, NFM_ESIZE, [&](auto d) {
+        return rec_launch<T, LogmFrechetOp<T, d()>>(x, g, nullptr, out, no, ni, p, stream);
+    });
 }
 
 } // namespace nfm
@@ -79,39 +59,34 @@ extern "C" {
 int nfm_lie_logm(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *x, const nfm_operand *out,
                  void *stream)
 {
-    int rc = logm_check(dtype, D, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {D});
     if (rc) return rc;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? logm_t<float>(D, nullptr, x, out, n_outer, n_inner, stream)
-                            : logm_t<double>(D, nullptr, x, out, n_outer, n_inner, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return logm_t<decltype(t)>(D, nullptr, x, out, n_outer, n_inner, stream);
+    });
 }
 
 int nfm_lie_logm_solve(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *m,
                        const nfm_operand *a, const nfm_operand *out, void *stream)
 {
-    int rc = logm_check(dtype, D, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {D});
     if (rc) return rc;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(m, dtype, nonempty))) return rc;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? logm_t<float>(D, m, a, out, n_outer, n_inner, stream)
-                            : logm_t<double>(D, m, a, out, n_outer, n_inner, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {m, a, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return logm_t<decltype(t)>(D, m, a, out, n_outer, n_inner, stream);
+    });
 }
 
 int nfm_lie_logm_frechet(int dtype, int D, int64_t n_outer, int64_t n_inner, const nfm_operand *x,
                          const nfm_operand *g, const nfm_operand *out, void *stream)
 {
-    int rc = logm_check(dtype, D, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {D});
     if (rc) return rc;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if ((rc = check_operand(g, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? logm_frechet_t<float>(D, x, g, out, n_outer, n_inner, stream)
-                            : logm_frechet_t<double>(D, x, g, out, n_outer, n_inner, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x, g, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return logm_frechet_t<decltype(t)>(D, x, g, out, n_outer, n_inner, stream);
+    });
 }
 
 } // extern "C"

@@ -364,24 +364,14 @@ __global__ __launch_bounds__(256) void householder_apply_kernel(Opnd a, Opnd u, 
 }
 
 // ------------------------------------------------------------------------- dispatch
-#define NFM_QR_CASE(Nv, ...)  \
-    case Nv: {                \
-        constexpr int N = Nv; \
-        __VA_ARGS__;          \
-    } break;
-#define NFM_QR_SWITCH8(Nexpr, ...)   \
-    switch (Nexpr) {                 \
-        NFM_QR_CASE(1, __VA_ARGS__)  \
-        NFM_QR_CASE(2, __VA_ARGS__)  \
-        NFM_QR_CASE(3, __VA_ARGS__)  \
-        NFM_QR_CASE(4, __VA_ARGS__)  \
-        NFM_QR_CASE(5, __VA_ARGS__)  \
-        NFM_QR_CASE(6, __VA_ARGS__)  \
-        NFM_QR_CASE(7, __VA_ARGS__)  \
-        NFM_QR_CASE(8, __VA_ARGS__)  \
-    default:                         \
-        break;                       \
-    }
+// orders 1..8: the register kernel `small(order constant)`; orders 9..16, and a register kernel that answers
+// NFM_EFALLBACK (a layout its only form does not cover): `large()`, the kernels of the other parts
+template <typename Small, typename Large>
+static int qr_by_order(int N, Small &&small, Large &&large)
+{
+    const int rc = switch_order<8>(N, NFM_EFALLBACK, small);
+    return rc != NFM_EFALLBACK ? rc : large();
+}
 
 template <typename T, int OP, int LANES>
 static int qr_lds_launch_l(const nfm_operand *a, const nfm_operand *b, void *out, int64_t out_rec, int64_t no, int64_t ni,
@@ -636,19 +626,23 @@ static int eig_sym_t(int N, int with_u, int fast, int64_t no, int64_t ni, const 
     nfm_operand o = packed_out(out, rec, ni);
     if constexpr (qr::FastSweeps<T>::on) {
         if (fast && with_u) {
-            NFM_QR_SWITCH8(N, return (rec_launch<T, EigSymOp<T, N, true, true>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-            return qr_generic_launch<T, QG_EIG_U_FAST>(a, nullptr, out, rec, no, ni, p, stream);
+            return qr_by_order(
+                N, [&](auto n) { return rec_launch<T, EigSymOp<T, n(), true, true>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+                [&] { return qr_generic_launch<T, QG_EIG_U_FAST>(a, nullptr, out, rec, no, ni, p, stream); });
         } else if (fast) {
-            NFM_QR_SWITCH8(N, return (rec_launch<T, EigSymOp<T, N, false, true>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-            return qr_generic_launch<T, QG_EIG_FAST>(a, nullptr, out, rec, no, ni, p, stream);
+            return qr_by_order(
+                N, [&](auto n) { return rec_launch<T, EigSymOp<T, n(), false, true>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+                [&] { return qr_generic_launch<T, QG_EIG_FAST>(a, nullptr, out, rec, no, ni, p, stream); });
         }
     }
     if (with_u) {
-        NFM_QR_SWITCH8(N, return (rec_launch<T, EigSymOp<T, N, true>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-        return qr_generic_launch<T, QG_EIG_U>(a, nullptr, out, rec, no, ni, p, stream);
+        return qr_by_order(
+            N, [&](auto n) { return rec_launch<T, EigSymOp<T, n(), true>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+            [&] { return qr_generic_launch<T, QG_EIG_U>(a, nullptr, out, rec, no, ni, p, stream); });
     }
-    NFM_QR_SWITCH8(N, return (rec_launch<T, EigSymOp<T, N, false>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-    return qr_generic_launch<T, QG_EIG>(a, nullptr, out, rec, no, ni, p, stream);
+    return qr_by_order(
+        N, [&](auto n) { return rec_launch<T, EigSymOp<T, n(), false>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+        [&] { return qr_generic_launch<T, QG_EIG>(a, nullptr, out, rec, no, ni, p, stream); });
 }
 
 template <typename T>
@@ -658,17 +652,21 @@ static int hess_t(int N, int sym, int with_u, int64_t no, int64_t ni, const nfm_
     const int64_t rec = N * N + (with_u ? upack_len(N) : 0);
     nfm_operand o = packed_out(out, rec, ni);
     if (sym && with_u) {
-        NFM_QR_SWITCH8(N, return (rec_launch<T, HessOp<T, N, true, true>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-        return qr_generic_launch<T, QG_HESSSYM_U>(a, nullptr, out, rec, no, ni, p, stream);
+        return qr_by_order(
+            N, [&](auto n) { return rec_launch<T, HessOp<T, n(), true, true>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+            [&] { return qr_generic_launch<T, QG_HESSSYM_U>(a, nullptr, out, rec, no, ni, p, stream); });
     } else if (sym) {
-        NFM_QR_SWITCH8(N, return (rec_launch<T, HessOp<T, N, true, false>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-        return qr_generic_launch<T, QG_HESSSYM>(a, nullptr, out, rec, no, ni, p, stream);
+        return qr_by_order(
+            N, [&](auto n) { return rec_launch<T, HessOp<T, n(), true, false>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+            [&] { return qr_generic_launch<T, QG_HESSSYM>(a, nullptr, out, rec, no, ni, p, stream); });
     } else if (with_u) {
-        NFM_QR_SWITCH8(N, return (rec_launch<T, HessOp<T, N, false, true>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-        return qr_generic_launch<T, QG_HESS_U>(a, nullptr, out, rec, no, ni, p, stream);
+        return qr_by_order(
+            N, [&](auto n) { return rec_launch<T, HessOp<T, n(), false, true>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+            [&] { return qr_generic_launch<T, QG_HESS_U>(a, nullptr, out, rec, no, ni, p, stream); });
     }
-    NFM_QR_SWITCH8(N, return (rec_launch<T, HessOp<T, N, false, false>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-    return qr_generic_launch<T, QG_HESS>(a, nullptr, out, rec, no, ni, p, stream);
+    return qr_by_order(
+        N, [&](auto n) { return rec_launch<T, HessOp<T, n(), false, false>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+        [&] { return qr_generic_launch<T, QG_HESS>(a, nullptr, out, rec, no, ni, p, stream); });
 }
 
 template <typename T>
@@ -676,8 +674,9 @@ static int qr_hess_t(int N, int64_t no, int64_t ni, const nfm_operand *a, void *
 {
     const int64_t rec = 2 * N * N;
     nfm_operand o = packed_out(out, rec, ni);
-    NFM_QR_SWITCH8(N, return (rec_launch<T, QrHessOp<T, N>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-    return qr_generic_launch<T, QG_QR>(a, nullptr, out, rec, no, ni, p, stream);
+    return qr_by_order(
+        N, [&](auto n) { return rec_launch<T, QrHessOp<T, n()>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+        [&] { return qr_generic_launch<T, QG_QR>(a, nullptr, out, rec, no, ni, p, stream); });
 }
 
 template <typename T>
@@ -690,18 +689,17 @@ static int rq_hess_t(int N, int64_t no, int64_t ni, const nfm_operand *a, const 
         // 8 x 8 float64 with U: two 128-register matrices plus the packed output.  Its mixed-layout kernel form
         // (per-operand mode branches) does not fit the register file, so only the contiguous form is built and
         // other layouts take the LDS-resident kernel, which reads any strides.
-        NFM_QR_SWITCH8(N, {
-            if constexpr (N == 8 && sizeof(T) == 8) {
-                const int rc = rec_launch<T, RqHessOp<T, N, true>, true>(a, u, nullptr, &o, no, ni, p, stream);
-                if (rc != NFM_EFALLBACK) return rc;
-            } else {
-                return (rec_launch<T, RqHessOp<T, N, true>>(a, u, nullptr, &o, no, ni, p, stream));
-            }
-        })
-        return qr_generic_launch<T, QG_RQ_U>(a, u, out, rec, no, ni, p, stream);
+        return qr_by_order(
+            N,
+            [&](auto n) {
+                constexpr bool fast_only = n() == 8 && sizeof(T) == 8;
+                return rec_launch<T, RqHessOp<T, n(), true>, fast_only>(a, u, nullptr, &o, no, ni, p, stream);
+            },
+            [&] { return qr_generic_launch<T, QG_RQ_U>(a, u, out, rec, no, ni, p, stream); });
     }
-    NFM_QR_SWITCH8(N, return (rec_launch<T, RqHessOp<T, N, false>>(a, nullptr, nullptr, &o, no, ni, p, stream)))
-    return qr_generic_launch<T, QG_RQ>(a, nullptr, out, rec, no, ni, p, stream);
+    return qr_by_order(
+        N, [&](auto n) { return rec_launch<T, RqHessOp<T, n(), false>>(a, nullptr, nullptr, &o, no, ni, p, stream); },
+        [&] { return qr_generic_launch<T, QG_RQ>(a, nullptr, out, rec, no, ni, p, stream); });
 }
 
 template <typename T>
@@ -710,8 +708,9 @@ static int householder_t(int N, int64_t no, int64_t ni, const nfm_operand *x, vo
 {
     const int64_t rec = N + 1;
     nfm_operand o = packed_out(out, rec, ni);
-    NFM_QR_SWITCH8(N, return (rec_launch<T, HouseholderOp<T, N>>(x, nullptr, nullptr, &o, no, ni, p, stream)))
-    return qr_generic_launch<T, QG_HH>(x, nullptr, out, rec, no, ni, p, stream);
+    return qr_by_order(
+        N, [&](auto n) { return rec_launch<T, HouseholderOp<T, n()>>(x, nullptr, nullptr, &o, no, ni, p, stream); },
+        [&] { return qr_generic_launch<T, QG_HH>(x, nullptr, out, rec, no, ni, p, stream); });
 }
 
 static QrParams mkparams(int n, int upper, int sym, int basis, int max_iter, double tol)
@@ -730,12 +729,11 @@ static QrParams mkparams(int n, int upper, int sym, int basis, int max_iter, dou
 
 using namespace nfm;
 
-#define QR_COMMON_CHECKS(N)                                   \
-    int rc = check_common(dtype, n_outer, n_inner);           \
-    if (rc) return rc;                                        \
-    if ((N) < 1 || (N) > NFM_MAX_DIM) return NFM_ESIZE;       \
-    const bool nonempty = n_outer > 0 && n_inner > 0;         \
-    (void)nonempty;
+// the raw pointer of the packed output buffer
+static int check_packed_out(const void *out, int64_t n_outer, int64_t n_inner)
+{
+    return n_outer > 0 && n_inner > 0 && out == nullptr ? NFM_EINVAL : NFM_OK;
+}
 
 extern "C" {
 
@@ -743,14 +741,16 @@ extern "C" {
 int nfm_qr_givens(int dtype, int64_t n_outer, int64_t n_inner, const nfm_operand *x, const nfm_operand *y, void *out,
                   void *stream)
 {
-    QR_COMMON_CHECKS(1)
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if ((rc = check_operand(y, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    int rc = check_batch(dtype, n_outer, n_inner, {1});
+    if (rc) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x, y}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     nfm_operand o = packed_out(out, 2, n_inner);
     QrParams p = mkparams(1, 0, 0, 0, 0, 0.0);
-    return dtype == NFM_F32 ? rec_launch<float, GivensOp<float>>(x, y, nullptr, &o, n_outer, n_inner, p, stream)
-                            : rec_launch<double, GivensOp<double>>(x, y, nullptr, &o, n_outer, n_inner, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return rec_launch<T, GivensOp<T>>(x, y, nullptr, &o, n_outer, n_inner, p, stream);
+    });
 }
 #endif
 
@@ -758,20 +758,17 @@ int nfm_qr_givens(int dtype, int64_t n_outer, int64_t n_inner, const nfm_operand
 int nfm_qr_givens_apply(int dtype, int N, int side, int i, int j, int64_t n_outer, int64_t n_inner,
                         const nfm_operand *a, const nfm_operand *c, const nfm_operand *s, void *stream)
 {
-    QR_COMMON_CHECKS(N)
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
     if (side < 0 || side > 2 || i < 0 || j < 0 || i >= N || j >= N) return NFM_EINVAL;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(c, dtype, nonempty))) return rc;
-    if ((rc = check_operand(s, dtype, nonempty))) return rc;
-    if (!nonempty) return NFM_OK;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a, c, s}))) return rc;
+    if (n_outer == 0 || n_inner == 0) return NFM_OK;
     dim3 grid((unsigned)((n_inner + 255) / 256), (unsigned)n_outer, 1);
-    if (dtype == NFM_F32)
-        hipLaunchKernelGGL((givens_apply_kernel<float>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+    return by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((givens_apply_kernel<decltype(t)>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
                            make_opnd(a, 0), make_opnd(c, 0), make_opnd(s, 0), n_inner, N, i, j, side);
-    else
-        hipLaunchKernelGGL((givens_apply_kernel<double>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
-                           make_opnd(a, 0), make_opnd(c, 0), make_opnd(s, 0), n_inner, N, i, j, side);
-    return launch_status();
+        return launch_status();
+    });
 }
 #endif
 
@@ -779,13 +776,15 @@ int nfm_qr_givens_apply(int dtype, int N, int side, int i, int j, int64_t n_oute
 int nfm_qr_householder(int dtype, int N, int basis, int64_t n_outer, int64_t n_inner, const nfm_operand *x,
                        void *out, void *stream)
 {
-    QR_COMMON_CHECKS(N)
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
     if (basis < 0 || basis >= N) return NFM_EINVAL;
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     QrParams p = mkparams(N, 0, 0, basis, 0, 0.0);
-    return dtype == NFM_F32 ? householder_t<float>(N, n_outer, n_inner, x, out, p, stream)
-                            : householder_t<double>(N, n_outer, n_inner, x, out, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return householder_t<decltype(t)>(N, n_outer, n_inner, x, out, p, stream);
+    });
 }
 #endif
 
@@ -793,19 +792,17 @@ int nfm_qr_householder(int dtype, int N, int basis, int64_t n_outer, int64_t n_i
 int nfm_qr_householder_apply(int dtype, int N, int m, int side, int64_t n_outer, int64_t n_inner,
                              const nfm_operand *a, const nfm_operand *u, void *stream)
 {
-    QR_COMMON_CHECKS(N)
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
     if (side < 0 || side > 2 || m < 1 || m > N) return NFM_EINVAL;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if ((rc = check_operand(u, dtype, nonempty))) return rc;
-    if (!nonempty) return NFM_OK;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a, u}))) return rc;
+    if (n_outer == 0 || n_inner == 0) return NFM_OK;
     dim3 grid((unsigned)((n_inner + 255) / 256), (unsigned)n_outer, 1);
-    if (dtype == NFM_F32)
-        hipLaunchKernelGGL((householder_apply_kernel<float>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
+    return by_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL((householder_apply_kernel<decltype(t)>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
                            make_opnd(a, 0), make_opnd(u, 0), n_inner, N, m, side);
-    else
-        hipLaunchKernelGGL((householder_apply_kernel<double>), grid, dim3(256), 0, static_cast<hipStream_t>(stream),
-                           make_opnd(a, 0), make_opnd(u, 0), n_inner, N, m, side);
-    return launch_status();
+        return launch_status();
+    });
 }
 #endif
 
@@ -813,12 +810,14 @@ int nfm_qr_householder_apply(int dtype, int N, int m, int side, int64_t n_outer,
 int nfm_qr_hessenberg(int dtype, int N, int sym, int upper, int with_u, int64_t n_outer, int64_t n_inner,
                       const nfm_operand *a, void *out, void *stream)
 {
-    QR_COMMON_CHECKS(N)
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     QrParams p = mkparams(N, upper ? 1 : 0, 0, 0, 0, 0.0);
-    return dtype == NFM_F32 ? hess_t<float>(N, sym, with_u, n_outer, n_inner, a, out, p, stream)
-                            : hess_t<double>(N, sym, with_u, n_outer, n_inner, a, out, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return hess_t<decltype(t)>(N, sym, with_u, n_outer, n_inner, a, out, p, stream);
+    });
 }
 #endif
 
@@ -826,12 +825,14 @@ int nfm_qr_hessenberg(int dtype, int N, int sym, int upper, int with_u, int64_t 
 int nfm_qr_qr_hessenberg(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *h, void *out,
                          void *stream)
 {
-    QR_COMMON_CHECKS(N)
-    if ((rc = check_operand(h, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {h}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     QrParams p = mkparams(N, 0, 0, 0, 0, 0.0);
-    return dtype == NFM_F32 ? qr_hess_t<float>(N, n_outer, n_inner, h, out, p, stream)
-                            : qr_hess_t<double>(N, n_outer, n_inner, h, out, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return qr_hess_t<decltype(t)>(N, n_outer, n_inner, h, out, p, stream);
+    });
 }
 #endif
 
@@ -839,13 +840,14 @@ int nfm_qr_qr_hessenberg(int dtype, int N, int64_t n_outer, int64_t n_inner, con
 int nfm_qr_rq_hessenberg(int dtype, int N, int sym, int64_t n_outer, int64_t n_inner, const nfm_operand *h,
                          const nfm_operand *u, void *out, void *stream)
 {
-    QR_COMMON_CHECKS(N)
-    if ((rc = check_operand(h, dtype, nonempty))) return rc;
-    if (u && (rc = check_operand(u, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {h, {u, u != nullptr}}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     QrParams p = mkparams(N, 0, sym ? 1 : 0, 0, 0, 0.0);
-    return dtype == NFM_F32 ? rq_hess_t<float>(N, n_outer, n_inner, h, u, out, p, stream)
-                            : rq_hess_t<double>(N, n_outer, n_inner, h, u, out, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return rq_hess_t<decltype(t)>(N, n_outer, n_inner, h, u, out, p, stream);
+    });
 }
 #endif
 
@@ -853,14 +855,16 @@ int nfm_qr_rq_hessenberg(int dtype, int N, int sym, int64_t n_outer, int64_t n_i
 int nfm_qr_eig_sym(int dtype, int N, int upper, int flags, int max_iter, double tol, int64_t n_outer,
                    int64_t n_inner, const nfm_operand *a, void *out, void *stream)
 {
-    QR_COMMON_CHECKS(N)
+    int rc = check_batch(dtype, n_outer, n_inner, {N});
+    if (rc) return rc;
     if (max_iter < 0 || flags < 0 || flags > (NFM_EIG_VECTORS | NFM_EIG_FAST)) return NFM_EINVAL;
     const int with_u = (flags & NFM_EIG_VECTORS) != 0, fast = (flags & NFM_EIG_FAST) != 0;
-    if ((rc = check_operand(a, dtype, nonempty))) return rc;
-    if (nonempty && out == nullptr) return NFM_EINVAL;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {a}))) return rc;
+    if ((rc = check_packed_out(out, n_outer, n_inner))) return rc;
     QrParams p = mkparams(N, upper ? 1 : 0, 1, 0, max_iter, tol);
-    return dtype == NFM_F32 ? eig_sym_t<float>(N, with_u, fast, n_outer, n_inner, a, out, p, stream)
-                            : eig_sym_t<double>(N, with_u, fast, n_outer, n_inner, a, out, p, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return eig_sym_t<decltype(t)>(N, with_u, fast, n_outer, n_inner, a, out, p, stream);
+    });
 }
 #endif
 

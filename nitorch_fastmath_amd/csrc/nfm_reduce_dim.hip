@@ -858,8 +858,10 @@ int nfm_reduce_moments(int dtype, int64_t outer, int64_t red, int64_t inner, con
         return moments_all_launch(dtype, x, red, workspace, out, s);
     }
     const FinParams f{out, NFM_F64, nullptr, -1, red};
-    if (dtype == NFM_F32) return run_dim<float, MomAcc<float>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
-    return run_dim<double, MomAcc<double>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return run_dim<T, MomAcc<T>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
+    });
 }
 
 int nfm_reduce_stat(int dtype, int stat, int out_dtype, int64_t outer, int64_t red, int64_t inner, const void *x,
@@ -871,8 +873,10 @@ int nfm_reduce_stat(int dtype, int stat, int out_dtype, int64_t outer, int64_t r
     if (st <= 0) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const FinParams f{out, out_dtype, nullptr, stat, red};
-    if (dtype == NFM_F32) return run_dim<float, MomAcc<float>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
-    return run_dim<double, MomAcc<double>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return run_dim<T, MomAcc<T>>(x, outer, red, inner, workspace, workspace_bytes, f, s);
+    });
 }
 
 } // extern "C"

@@ -594,8 +594,9 @@ int nfm_reduce_median(int dtype, int omitnan, int64_t rows, int64_t red, const v
     if (rows < 0 || red < 0) return NFM_EINVAL;
     if (rows == 0) return NFM_OK;
     if (red == 0 || x == nullptr || val == nullptr) return NFM_EINVAL;
-    return dtype == NFM_F32 ? med::run<float>(omitnan ? 1 : 0, rows, red, x, workspace, workspace_bytes, val, idx, stream)
-                            : med::run<double>(omitnan ? 1 : 0, rows, red, x, workspace, workspace_bytes, val, idx, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return med::run<decltype(t)>(omitnan ? 1 : 0, rows, red, x, workspace, workspace_bytes, val, idx, stream);
+    });
 }
 
 } // extern "C"

@@ -353,7 +353,7 @@ int nfm_simplex_forward(int dtype, int op, int flags, int implicit_index, int64_
     p.a = x;
     p.o = only_lse ? nullptr : out;
     p.l = lse;
-    return dtype == NFM_F32 ? simplex::dispatch<float, false>(p, stream) : simplex::dispatch<double, false>(p, stream);
+    return by_dtype(dtype, [&](auto t) { return simplex::dispatch<decltype(t), false>(p, stream); });
 }
 
 int nfm_simplex_backward(int dtype, int op, int flags, int implicit_index, int64_t outer, int64_t K, int64_t inner,
@@ -391,7 +391,7 @@ int nfm_simplex_backward(int dtype, int op, int flags, int implicit_index, int64
     p.a = saved;
     p.g = grad_output;
     p.o = grad_input;
-    return dtype == NFM_F32 ? simplex::dispatch<float, true>(p, stream) : simplex::dispatch<double, true>(p, stream);
+    return by_dtype(dtype, [&](auto t) { return simplex::dispatch<decltype(t), true>(p, stream); });
 }
 
 } // extern "C"

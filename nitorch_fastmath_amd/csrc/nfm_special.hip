@@ -185,8 +185,7 @@ static int besseli_entry(bool host, int dtype, int mode, double nu, int64_t n, c
     const void *ptrs[] = {z, out};
     if (int rc = check(dtype, mode < 0 || mode > 2 || bad_nu(nu), false, n, ptrs, 2)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? besseli_fwd<float>(host, mode, nu, n, z, out, stream)
-                            : besseli_fwd<double>(host, mode, nu, n, z, out, stream);
+    return by_dtype(dtype, [&](auto t) { return besseli_fwd<decltype(t)>(host, mode, nu, n, z, out, stream); });
 }
 
 static int besseli_bwd_entry(bool host, int dtype, int mode, double nu, int64_t n, const void *z, const void *out,
@@ -195,8 +194,9 @@ static int besseli_bwd_entry(bool host, int dtype, int mode, double nu, int64_t 
     const void *ptrs[] = {z, out, grad_out, grad_z};
     if (int rc = check(dtype, mode < 0 || mode > 2 || bad_nu(nu), false, n, ptrs, 4)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? besseli_bwd_any<float>(host, mode, nu, n, z, out, grad_out, grad_z, stream)
-                            : besseli_bwd_any<double>(host, mode, nu, n, z, out, grad_out, grad_z, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return besseli_bwd_any<decltype(t)>(host, mode, nu, n, z, out, grad_out, grad_z, stream);
+    });
 }
 
 static int ratio_entry(bool host, int dtype, double nu, int N, int K, int64_t n, const void *x, void *out, void *stream)
@@ -204,8 +204,7 @@ static int ratio_entry(bool host, int dtype, double nu, int N, int K, int64_t n,
     const void *ptrs[] = {x, out};
     if (int rc = check(dtype, bad_nu(nu) || N < 0 || K < 0, N > kMaxN, n, ptrs, 2)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? ratio_fwd<float>(host, nu, N, K, n, x, out, stream)
-                            : ratio_fwd<double>(host, nu, N, K, n, x, out, stream);
+    return by_dtype(dtype, [&](auto t) { return ratio_fwd<decltype(t)>(host, nu, N, K, n, x, out, stream); });
 }
 
 static int ratio_bwd_entry(bool host, int dtype, double nu, int64_t n, const void *x, const void *out, const void *grad_out,
@@ -214,8 +213,10 @@ static int ratio_bwd_entry(bool host, int dtype, double nu, int64_t n, const voi
     const void *ptrs[] = {x, out, grad_out, grad_x};
     if (int rc = check(dtype, bad_nu(nu), false, n, ptrs, 4)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? run<float, 3>(RatioBwdF<float>{nu}, host, x, out, grad_out, grad_x, n, stream)
-                            : run<double, 3>(RatioBwdF<double>{nu}, host, x, out, grad_out, grad_x, n, stream);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return run<T, 3>(RatioBwdF<T>{nu}, host, x, out, grad_out, grad_x, n, stream);
+    });
 }
 
 static int digamma_entry(bool host, int dtype, int order, int64_t n, const void *x, void *out, void *stream)
@@ -223,8 +224,10 @@ static int digamma_entry(bool host, int dtype, int order, int64_t n, const void 
     const void *ptrs[] = {x, out};
     if (int rc = check(dtype, order < 1, false, n, ptrs, 2)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? run<float, 1>(DigammaF<float>{order}, host, x, nullptr, nullptr, out, n, stream)
-                            : run<double, 1>(DigammaF<double>{order}, host, x, nullptr, nullptr, out, n, stream);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return run<T, 1>(DigammaF<T>{order}, host, x, nullptr, nullptr, out, n, stream);
+    });
 }
 
 static int digamma_bwd_entry(bool host, int dtype, int order, int64_t n, const void *x, const void *grad_out, void *grad_x,
@@ -233,8 +236,10 @@ static int digamma_bwd_entry(bool host, int dtype, int order, int64_t n, const v
     const void *ptrs[] = {x, grad_out, grad_x};
     if (int rc = check(dtype, order < 1, false, n, ptrs, 3)) return rc;
     if (n == 0) return NFM_OK;
-    return dtype == NFM_F32 ? run<float, 2>(TrigammaF<float>{order}, host, x, grad_out, nullptr, grad_x, n, stream)
-                            : run<double, 2>(TrigammaF<double>{order}, host, x, grad_out, nullptr, grad_x, n, stream);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return run<T, 2>(TrigammaF<T>{order}, host, x, grad_out, nullptr, grad_x, n, stream);
+    });
 }
 
 } // namespace special

@@ -9,27 +9,6 @@
 
 namespace nfm {
 
-// ------------------------------------------------------------------- dispatch helpers
-#define NFM_CASE_M(Mv, ...) \
-    case Mv: {              \
-        constexpr int M = Mv; \
-        __VA_ARGS__;        \
-    } break;
-
-#define NFM_SWITCH_M8(Mexpr, ...)        \
-    switch (Mexpr) {                     \
-        NFM_CASE_M(1, __VA_ARGS__)       \
-        NFM_CASE_M(2, __VA_ARGS__)       \
-        NFM_CASE_M(3, __VA_ARGS__)       \
-        NFM_CASE_M(4, __VA_ARGS__)       \
-        NFM_CASE_M(5, __VA_ARGS__)       \
-        NFM_CASE_M(6, __VA_ARGS__)       \
-        NFM_CASE_M(7, __VA_ARGS__)       \
-        NFM_CASE_M(8, __VA_ARGS__)       \
-    default:                             \
-        return NFM_ESIZE;                \
-    }
-
 // One matrix (per outer slab) solved against many vectors (M <= 8).  Closed forms (M <= 4): the cofactors and
 // the determinant are derived once per lane and applied to V right-hand sides -- the same operations
 // in the same order as SolveOp (sym_solve_prepare / sym_solve_apply are the two halves of
@@ -366,6 +345,16 @@ static int sym_bcast_big(int M, int kind, int mode, int64_t no, int64_t ni, cons
     return launch_status();
 }
 
+// orders 1..8 of the ops with a matrix kind (SolveOp, MatvecOp): one matrix per lane in registers
+template <typename T, template <typename, int, int> class Op, int KIND, typename P>
+static int sym_small(int M, const nfm_operand *mat, const nfm_operand *vec, const nfm_operand *inp,
+                     const nfm_operand *out, int64_t no, int64_t ni, const P &p, void *stream)
+{
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return rec_launch<T, Op<T, m(), KIND>>(mat, vec, inp, out, no, ni, p, stream);
+    });
+}
+
 template <typename T>
 static int sym_solve_t(int M, int kind, int64_t no, int64_t ni, const nfm_operand *mat, const nfm_operand *vec,
                        const nfm_operand *out, const SolveParams &p, void *stream, bool pivoted = false)
@@ -404,22 +393,12 @@ static int sym_solve_t(int M, int kind, int64_t no, int64_t ni, const nfm_operan
         return big_sym_solve<T>(M, kind, no, ni, mat, vec, out, p.has_eps ? p.eps : nullptr, stream);
     }
     switch (kind) {
-    case NFM_MAT_SYM:
-        NFM_SWITCH_M8(M, return (rec_launch<T, SolveOp<T, M, NFM_MAT_SYM>>(mat, vec, nullptr, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_DIAG:
-        NFM_SWITCH_M8(M, return (rec_launch<T, SolveOp<T, M, NFM_MAT_DIAG>>(mat, vec, nullptr, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_SCAL:
-        NFM_SWITCH_M8(M, return (rec_launch<T, SolveOp<T, M, NFM_MAT_SCAL>>(mat, vec, nullptr, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_FULL:
-        NFM_SWITCH_M8(M, return (rec_launch<T, SolveOp<T, M, NFM_MAT_FULL>>(mat, vec, nullptr, out, no, ni, p, stream)))
-        break;
-    default:
-        return NFM_EINVAL;
+    case NFM_MAT_SYM: return sym_small<T, SolveOp, NFM_MAT_SYM>(M, mat, vec, nullptr, out, no, ni, p, stream);
+    case NFM_MAT_DIAG: return sym_small<T, SolveOp, NFM_MAT_DIAG>(M, mat, vec, nullptr, out, no, ni, p, stream);
+    case NFM_MAT_SCAL: return sym_small<T, SolveOp, NFM_MAT_SCAL>(M, mat, vec, nullptr, out, no, ni, p, stream);
+    case NFM_MAT_FULL: return sym_small<T, SolveOp, NFM_MAT_FULL>(M, mat, vec, nullptr, out, no, ni, p, stream);
+    default: return NFM_EINVAL;
     }
-    return NFM_EINVAL;
 }
 
 template <typename T>
@@ -447,22 +426,12 @@ static int sym_matvec_t(int M, int kind, int mode, int64_t no, int64_t ni, const
     }
     MatvecParams p{mode};
     switch (kind) {
-    case NFM_MAT_SYM:
-        NFM_SWITCH_M8(M, return (rec_launch<T, MatvecOp<T, M, NFM_MAT_SYM>>(mat, vec, inp, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_DIAG:
-        NFM_SWITCH_M8(M, return (rec_launch<T, MatvecOp<T, M, NFM_MAT_DIAG>>(mat, vec, inp, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_SCAL:
-        NFM_SWITCH_M8(M, return (rec_launch<T, MatvecOp<T, M, NFM_MAT_SCAL>>(mat, vec, inp, out, no, ni, p, stream)))
-        break;
-    case NFM_MAT_FULL:
-        NFM_SWITCH_M8(M, return (rec_launch<T, MatvecOp<T, M, NFM_MAT_FULL>>(mat, vec, inp, out, no, ni, p, stream)))
-        break;
-    default:
-        return NFM_EINVAL;
+    case NFM_MAT_SYM: return sym_small<T, MatvecOp, NFM_MAT_SYM>(M, mat, vec, inp, out, no, ni, p, stream);
+    case NFM_MAT_DIAG: return sym_small<T, MatvecOp, NFM_MAT_DIAG>(M, mat, vec, inp, out, no, ni, p, stream);
+    case NFM_MAT_SCAL: return sym_small<T, MatvecOp, NFM_MAT_SCAL>(M, mat, vec, inp, out, no, ni, p, stream);
+    case NFM_MAT_FULL: return sym_small<T, MatvecOp, NFM_MAT_FULL>(M, mat, vec, inp, out, no, ni, p, stream);
+    default: return NFM_EINVAL;
     }
-    return NFM_EINVAL;
 }
 
 template <typename T>
@@ -488,12 +457,10 @@ static int sym_invert_t(int M, int flags, int64_t no, int64_t ni, const nfm_oper
         return big_sym_invert<T>(M, diag_only, no, ni, mat, out, stream);
     }
     NoParams p{0};
-    if (diag_only) {
-        NFM_SWITCH_M8(M, return (rec_launch<T, InvertOp<T, M, true>>(mat, nullptr, nullptr, out, no, ni, p, stream)))
-    } else {
-        NFM_SWITCH_M8(M, return (rec_launch<T, InvertOp<T, M, false>>(mat, nullptr, nullptr, out, no, ni, p, stream)))
-    }
-    return NFM_EINVAL;
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return diag_only ? rec_launch<T, InvertOp<T, m(), true>>(mat, nullptr, nullptr, out, no, ni, p, stream)
+                         : rec_launch<T, InvertOp<T, m(), false>>(mat, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T>
@@ -512,8 +479,9 @@ static int sym_det_t(int M, int64_t no, int64_t ni, const nfm_operand *mat, cons
         return big_sym_det<T>(M, no, ni, mat, out, stream);
     }
     NoParams p{0};
-    NFM_SWITCH_M8(M, return (rec_launch<T, DetOp<T, M>>(mat, nullptr, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return rec_launch<T, DetOp<T, m()>>(mat, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T>
@@ -522,8 +490,9 @@ static int sym_to_full_t(int M, int64_t no, int64_t ni, const nfm_operand *mat, 
 {
     if (M > 8) return big_sym_to_full<T>(M, no, ni, mat, out, stream);
     NoParams p{0};
-    NFM_SWITCH_M8(M, return (rec_launch<T, ToFullOp<T, M>>(mat, nullptr, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return rec_launch<T, ToFullOp<T, m()>>(mat, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T>
@@ -531,8 +500,9 @@ static int sym_outer_t(int M, int64_t no, int64_t ni, const nfm_operand *x, cons
 {
     if (M > 8) return big_sym_outer<T>(M, no, ni, x, out, stream);
     NoParams p{0};
-    NFM_SWITCH_M8(M, return (rec_launch<T, OuterOp<T, M>>(x, nullptr, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return rec_launch<T, OuterOp<T, m()>>(x, nullptr, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T>
@@ -541,8 +511,9 @@ static int sym_outer2_t(int M, int neg, int64_t no, int64_t ni, const nfm_operan
 {
     if (M > 8) return big_sym_outer2<T>(M, neg, no, ni, x, y, out, stream);
     Outer2Params p{neg};
-    NFM_SWITCH_M8(M, return (rec_launch<T, Outer2Op<T, M>>(x, y, nullptr, out, no, ni, p, stream)))
-    return NFM_EINVAL;
+    return switch_order<8>(M, NFM_ESIZE, [&](auto m) {
+        return rec_launch<T, Outer2Op<T, m()>>(x, y, nullptr, out, no, ni, p, stream);
+    });
 }
 
 template <typename T, int HK>
@@ -550,15 +521,12 @@ static int sym_matmul_t(int K, int D, int64_t no, int64_t ni, const nfm_operand 
                         const nfm_operand *out, void *stream)
 {
     NoParams p{0};
-#define NFM_MM(Kv, Dv)                                                                              \
-    if (K == Kv && D == Dv)                                                                         \
-        return (rec_launch<T, MatmulOp<T, Kv, Dv, HK>>(jac, hess, nullptr, out, no, ni, p, stream));
-    NFM_MM(1, 1) NFM_MM(1, 2) NFM_MM(1, 3) NFM_MM(1, 4)
-    NFM_MM(2, 1) NFM_MM(2, 2) NFM_MM(2, 3) NFM_MM(2, 4)
-    NFM_MM(3, 1) NFM_MM(3, 2) NFM_MM(3, 3) NFM_MM(3, 4)
-    NFM_MM(4, 1) NFM_MM(4, 2) NFM_MM(4, 3) NFM_MM(4, 4)
-#undef NFM_MM
-    return big_sym_matmul<T>(K, D, HK, no, ni, jac, hess, out, stream);
+    if (K > 4 || D > 4) return big_sym_matmul<T>(K, D, HK, no, ni, jac, hess, out, stream);
+    return switch_order<4>(K, NFM_ESIZE, [&](auto k) {
+        return switch_order<4>(D, NFM_ESIZE, [&](auto d) {
+            return rec_launch<T, MatmulOp<T, decltype(k)::value, d(), HK>>(jac, hess, nullptr, out, no, ni, p, stream);
+        });
+    });
 }
 
 } // namespace nfm
@@ -570,125 +538,101 @@ extern "C" {
 int nfm_sym_solve(int dtype, int M, int mat_kind, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
                   const nfm_operand *vec, const nfm_operand *out, const double *eps, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
     const bool pivoted = (mat_kind & NFM_MAT_PIVOTED) != 0;
     mat_kind &= ~NFM_MAT_PIVOTED;
     if (mat_kind < 0 || mat_kind > 3) return NFM_EINVAL;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(mat, dtype, nonempty))) return rc;
-    if ((rc = check_operand(vec, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {mat, vec, out}))) return rc;
     SolveParams p;
     p.has_eps = eps != nullptr;
     for (int i = 0; i < NFM_MAX_DIM; ++i) p.eps[i] = (eps && i < M) ? eps[i] : 0.0;
-    return dtype == NFM_F32 ? sym_solve_t<float>(M, mat_kind, n_outer, n_inner, mat, vec, out, p, stream, pivoted)
-                            : sym_solve_t<double>(M, mat_kind, n_outer, n_inner, mat, vec, out, p, stream, pivoted);
+    return by_dtype(dtype, [&](auto t) {
+        return sym_solve_t<decltype(t)>(M, mat_kind, n_outer, n_inner, mat, vec, out, p, stream, pivoted);
+    });
 }
 
 int nfm_sym_matvec(int dtype, int M, int mat_kind, int mode, int64_t n_outer, int64_t n_inner,
                    const nfm_operand *mat, const nfm_operand *vec, const nfm_operand *inp, const nfm_operand *out,
                    void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
     if (mat_kind < 0 || mat_kind > 3 || mode < -1 || mode > 1) return NFM_EINVAL;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(mat, dtype, nonempty))) return rc;
-    if ((rc = check_operand(vec, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    if (mode != 0 && (rc = check_operand(inp, dtype, nonempty))) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {mat, vec, out, {inp, mode != 0}}))) return rc;
     if (mode == 0) inp = nullptr;
-    return dtype == NFM_F32 ? sym_matvec_t<float>(M, mat_kind, mode, n_outer, n_inner, mat, vec, inp, out, stream)
-                            : sym_matvec_t<double>(M, mat_kind, mode, n_outer, n_inner, mat, vec, inp, out, stream);
+    return by_dtype(dtype, [&](auto t) {
+        return sym_matvec_t<decltype(t)>(M, mat_kind, mode, n_outer, n_inner, mat, vec, inp, out, stream);
+    });
 }
 
 int nfm_sym_invert(int dtype, int M, int diag_only, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
                    const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(mat, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? sym_invert_t<float>(M, diag_only, n_outer, n_inner, mat, out, stream)
-                            : sym_invert_t<double>(M, diag_only, n_outer, n_inner, mat, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {mat, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return sym_invert_t<decltype(t)>(M, diag_only, n_outer, n_inner, mat, out, stream);
+    });
 }
 
 int nfm_sym_det(int dtype, int M, int64_t n_outer, int64_t n_inner, const nfm_operand *mat, const nfm_operand *out,
                 void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(mat, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? sym_det_t<float>(M, n_outer, n_inner, mat, out, stream)
-                            : sym_det_t<double>(M, n_outer, n_inner, mat, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {mat, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return sym_det_t<decltype(t)>(M, n_outer, n_inner, mat, out, stream);
+    });
 }
 
 int nfm_sym_to_full(int dtype, int M, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
                     const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(mat, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? sym_to_full_t<float>(M, n_outer, n_inner, mat, out, stream)
-                            : sym_to_full_t<double>(M, n_outer, n_inner, mat, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {mat, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return sym_to_full_t<decltype(t)>(M, n_outer, n_inner, mat, out, stream);
+    });
 }
 
 int nfm_sym_outer(int dtype, int M, int64_t n_outer, int64_t n_inner, const nfm_operand *x, const nfm_operand *out,
                   void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? sym_outer_t<float>(M, n_outer, n_inner, x, out, stream)
-                            : sym_outer_t<double>(M, n_outer, n_inner, x, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return sym_outer_t<decltype(t)>(M, n_outer, n_inner, x, out, stream);
+    });
 }
 
 int nfm_sym_outer2(int dtype, int M, int neg, int64_t n_outer, int64_t n_inner, const nfm_operand *x,
                    const nfm_operand *y, const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (M < 1 || M > NFM_MAX_DIM) return NFM_ESIZE;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(x, dtype, nonempty))) return rc;
-    if ((rc = check_operand(y, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    return dtype == NFM_F32 ? sym_outer2_t<float>(M, neg ? 1 : 0, n_outer, n_inner, x, y, out, stream)
-                            : sym_outer2_t<double>(M, neg ? 1 : 0, n_outer, n_inner, x, y, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {x, y, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        return sym_outer2_t<decltype(t)>(M, neg ? 1 : 0, n_outer, n_inner, x, y, out, stream);
+    });
 }
 
 int nfm_sym_matmul(int dtype, int K, int D, int hess_kind, int64_t n_outer, int64_t n_inner,
                    const nfm_operand *jac, const nfm_operand *hess, const nfm_operand *out, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {K, D});
     if (rc) return rc;
-    if (K < 1 || K > NFM_MAX_DIM || D < 1 || D > NFM_MAX_DIM) return NFM_ESIZE;
     if (hess_kind != NFM_MAT_SYM && hess_kind != NFM_MAT_DIAG) return NFM_EINVAL;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(jac, dtype, nonempty))) return rc;
-    if ((rc = check_operand(hess, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
-    if (dtype == NFM_F32)
-        return hess_kind == NFM_MAT_SYM
-                   ? sym_matmul_t<float, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, out, stream)
-                   : sym_matmul_t<float, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, out, stream);
-    return hess_kind == NFM_MAT_SYM
-               ? sym_matmul_t<double, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, out, stream)
-               : sym_matmul_t<double, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, out, stream);
+    if ((rc = check_operands(dtype, n_outer, n_inner, {jac, hess, out}))) return rc;
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return hess_kind == NFM_MAT_SYM ? sym_matmul_t<T, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, out, stream)
+                                        : sym_matmul_t<T, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, out, stream);
+    });
 }
 
 } // extern "C"

@@ -28,15 +28,11 @@ template <typename T, int HK>
 static int matmul_solve_t(int K, int D, int64_t no, int64_t ni, const nfm_operand *jac, const nfm_operand *hess,
                           const nfm_operand *grad, const nfm_operand *out, const SolveParams &p, void *stream)
 {
-#define NFM_MS(Kv, Dv)                                                                                   \
-    if (K == Kv && D == Dv)                                                                              \
-        return (rec_launch<T, MatmulSolveOp<T, Kv, Dv, HK>>(jac, hess, grad, out, no, ni, p, stream));
-    NFM_MS(1, 1) NFM_MS(1, 2) NFM_MS(1, 3) NFM_MS(1, 4)
-    NFM_MS(2, 1) NFM_MS(2, 2) NFM_MS(2, 3) NFM_MS(2, 4)
-    NFM_MS(3, 1) NFM_MS(3, 2) NFM_MS(3, 3) NFM_MS(3, 4)
-    NFM_MS(4, 1) NFM_MS(4, 2) NFM_MS(4, 3) NFM_MS(4, 4)
-#undef NFM_MS
-    return NFM_ESIZE;
+    return switch_order<4>(K, NFM_ESIZE, [&](auto k) {
+        return switch_order<4>(D, NFM_ESIZE, [&](auto d) {
+            return rec_launch<T, MatmulSolveOp<T, decltype(k)::value, d(), HK>>(jac, hess, grad, out, no, ni, p, stream);
+        });
+    });
 }
 
 } // namespace nfm
@@ -47,23 +43,17 @@ extern "C" int nfm_sym_matmul_solve(int dtype, int K, int D, int hess_kind, int6
                                     const nfm_operand *jac, const nfm_operand *hess, const nfm_operand *grad,
                                     const nfm_operand *out, const double *eps, void *stream)
 {
-    int rc = check_common(dtype, n_outer, n_inner);
+    int rc = check_batch(dtype, n_outer, n_inner, {K, D}, 4);
     if (rc) return rc;
-    if (K < 1 || K > 4 || D < 1 || D > 4) return NFM_ESIZE;
     if (hess_kind != NFM_MAT_SYM && hess_kind != NFM_MAT_DIAG) return NFM_EINVAL;
-    const bool nonempty = n_outer > 0 && n_inner > 0;
-    if ((rc = check_operand(jac, dtype, nonempty))) return rc;
-    if ((rc = check_operand(hess, dtype, nonempty))) return rc;
-    if ((rc = check_operand(grad, dtype, nonempty))) return rc;
-    if ((rc = check_operand(out, dtype, nonempty))) return rc;
+    if ((rc = check_operands(dtype, n_outer, n_inner, {jac, hess, grad, out}))) return rc;
     SolveParams p;
     p.has_eps = eps != nullptr;
     for (int i = 0; i < NFM_MAX_DIM; ++i) p.eps[i] = (eps && i < D) ? eps[i] : 0.0;
-    if (dtype == NFM_F32)
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
         return hess_kind == NFM_MAT_SYM
-                   ? matmul_solve_t<float, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream)
-                   : matmul_solve_t<float, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream);
-    return hess_kind == NFM_MAT_SYM
-               ? matmul_solve_t<double, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream)
-               : matmul_solve_t<double, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream);
+                   ? matmul_solve_t<T, NFM_MAT_SYM>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream)
+                   : matmul_solve_t<T, NFM_MAT_DIAG>(K, D, n_outer, n_inner, jac, hess, grad, out, p, stream);
+    });
 }

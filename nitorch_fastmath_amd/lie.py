@@ -15,11 +15,9 @@ derivatives the block identities
 `logm` and `meanm` are not names of this module: they live in `nitorch_fastmath_amd.logm`.
 """
 __all__ = ['expm', 'expm_derivatives']
-import ctypes
 import torch
 from . import _lib
-from ._dispatch import (on_device, Batch, broadcast_shapes, common_dtype, dtype_code, expand_batch,
-                        no_grad_required, require_gpu, same_dtype, stream_ptr)
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, no_grad_required, prepare
 
 FORWARD_MAX = {torch.float32: 8, torch.float64: 7}   # orders with an expm kernel (include/nfm_hip.h)
 FRECHET_MAX = 4                                       # orders with a Frechet kernel
@@ -30,15 +28,6 @@ def __getattr__(name):
         raise AttributeError(f'nitorch_fastmath_amd.lie does not provide {name}: import it from '
                              f'nitorch_fastmath_amd.logm (`from nitorch_fastmath_amd.logm import {name}`)')
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
-
-
-def _check(*tensors):
-    """device and dtype checks of the facade (float32 / float64 GPU tensors); returns (device, dtype, tensors)"""
-    tensors = [None if t is None else torch.as_tensor(t) for t in tensors]
-    dev = require_gpu(*tensors)
-    dtype = common_dtype(None, *tensors)
-    dtype_code(dtype)
-    return dev, dtype, same_dtype(tensors, dtype)
 
 
 def _compose(X, basis):
@@ -67,11 +56,7 @@ def _expm(M, max_order, tol):
     batch = M.shape[:-2]
     out = torch.empty(tuple(batch) + (D, D), dtype=M.dtype, device=dev)
     b = Batch(batch, [M, out], [2, 2])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_lie_expm(dtype_code(M.dtype), D, max_order, tol, b.n_outer, b.n_inner,
-                                           ctypes.byref(o[0]), ctypes.byref(o[1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_lie_expm, dev, M.dtype, (D, max_order, tol), b)
     return out
 
 
@@ -102,13 +87,7 @@ def _frechet(M, A, B, max_order, tol):
     batch = broadcast_shapes(*[t.shape[:-2] for t in ops])
     out = torch.empty(tuple(batch) + (D, D), dtype=M.dtype, device=dev)
     b = Batch(batch, [expand_batch(batch, t, 2) for t in ops] + [out], [2] * (len(ops) + 1))
-    o = b.operands
-    ob = None if B is None else ctypes.byref(o[2])
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_lie_expm_frechet(dtype_code(M.dtype), D, max_order, tol, b.n_outer, b.n_inner,
-                                                   ctypes.byref(o[0]), ctypes.byref(o[1]), ob,
-                                                   ctypes.byref(o[-1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_lie_expm_frechet, dev, M.dtype, (D, max_order, tol), b, (0, 1, None if B is None else 2, -1))
     return out
 
 
@@ -120,9 +99,9 @@ def expm(X, basis=None, max_order=10000, tol=1e-32):
         `sum(T_n^2) <= D^2 tol` (at most `max_order`), after scaling by 2^-s.
     Returns `(..., D, D)`.  Differentiable: the backward runs the Frechet kernel, L(M^T, G).
     """
-    from ._autograd import ExpmFn, needs_grad
+    from ._autograd import ExpmFn
     max_order, tol = _limits(max_order, tol)
-    _, _, (X, basis) = _check(X, basis)
+    _, _, (X, basis) = prepare(None, X, basis, grad_ok=True)
     M = X if basis is None else _compose(X, basis)
     if M.shape[-2] != M.shape[-1]:
         raise ValueError(f'expected square matrices, got {tuple(M.shape[-2:])}')
@@ -144,7 +123,7 @@ def expm_derivatives(X, basis=None, grad_X=False, grad_basis=False, hess_X=False
     (also for a batched X, where the reference raises: Q19).
     """
     max_order, tol = _limits(max_order, tol)
-    dev, dtype, (X, basis) = _check(X, basis)
+    dev, dtype, (X, basis) = prepare(None, X, basis, grad_ok=True)
     no_grad_required(X, basis)
     if basis is None:
         D = X.shape[-1]

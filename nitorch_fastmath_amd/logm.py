@@ -14,26 +14,16 @@ closed negative real axis) gives NaN in every entry, where the reference returns
 complex result.
 """
 __all__ = ['logm', 'meanm']
-import ctypes
 import warnings
 import torch
 from . import _lib
-from ._dispatch import (on_device, Batch, broadcast_shapes, common_dtype, dtype_code, expand_batch,
-                        require_gpu, same_dtype, stream_ptr)
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
 
 FORWARD_MAX = {torch.float32: 8, torch.float64: 7}   # orders with a logm / logm_solve kernel (include/nfm_hip.h)
 FRECHET_MAX = 5                                       # orders with a Frechet kernel
 THETA = 0.25                                          # square roots until ||A - I||_1 <= THETA
 MAX_ITER = 40                                         # Denman-Beavers steps per square root
 MAX_ROOTS = 64
-
-
-def _check(*tensors):
-    tensors = [None if t is None else torch.as_tensor(t) for t in tensors]
-    dev = require_gpu(*tensors)
-    dtype = common_dtype(None, *tensors)
-    dtype_code(dtype)
-    return dev, dtype, same_dtype(tensors, dtype)
 
 
 def _square(M):
@@ -133,17 +123,8 @@ def _logm(A, M=None):
     batch = broadcast_shapes(*[t.shape[:-2] for t in ops])
     out = torch.empty(tuple(batch) + (D, D), dtype=A.dtype, device=dev)
     b = Batch(batch, [expand_batch(batch, t, 2) for t in ops] + [out], [2] * (len(ops) + 1))
-    o = b.operands
     L = _lib.lib()
-    with on_device(dev):
-        if M is None:
-            rc = L.nfm_lie_logm(dtype_code(A.dtype), D, b.n_outer, b.n_inner, ctypes.byref(o[0]),
-                                ctypes.byref(o[1]), stream_ptr(dev))
-        else:
-            rc = L.nfm_lie_logm_solve(dtype_code(A.dtype), D, b.n_outer, b.n_inner, ctypes.byref(o[0]),
-                                      ctypes.byref(o[1]), ctypes.byref(o[2]), stream_ptr(dev))
-        _lib.check(rc)
-    b.finish()
+    launch(L.nfm_lie_logm if M is None else L.nfm_lie_logm_solve, dev, A.dtype, (D,), b)
     return out
 
 
@@ -154,11 +135,7 @@ def _frechet(X, G):
     batch = broadcast_shapes(X.shape[:-2], G.shape[:-2])
     out = torch.empty(tuple(batch) + (D, D), dtype=X.dtype, device=dev)
     b = Batch(batch, [expand_batch(batch, X, 2), expand_batch(batch, G, 2), out], [2, 2, 2])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_lie_logm_frechet(dtype_code(X.dtype), D, b.n_outer, b.n_inner, ctypes.byref(o[0]),
-                                                   ctypes.byref(o[1]), ctypes.byref(o[2]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_lie_logm_frechet, dev, X.dtype, (D,), b)
     return out
 
 
@@ -170,8 +147,8 @@ def logm(mat):
     logarithm gives NaN in every entry (Q22).  Differentiable: the backward is L_log(X^T, G), the Frechet
     kernel at orders 1..5 and autograd through the torch route above them.
     """
-    from ._autograd import LogmFn, needs_grad
-    _, _, (mat,) = _check(mat)
+    from ._autograd import LogmFn
+    _, _, (mat,) = prepare(None, mat, grad_ok=True)
     D = _square(mat)
     if needs_grad(mat):
         if D > FRECHET_MAX:
@@ -198,7 +175,7 @@ def _meanm(mats, max_iter, tol):
     from .lie import _expm
     if not torch.is_tensor(mats):
         mats = torch.stack(list(mats))
-    _check(mats)
+    prepare(None, mats, grad_ok=True)
     D = _square(mats)
     if mats.dim() < 3:
         raise ValueError(f'expected (..., N, M, M) matrices, got {tuple(mats.shape)}')

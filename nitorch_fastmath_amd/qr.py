@@ -40,10 +40,9 @@ __all__ = [
     'givens',
     'givens_apply',
 ]
-import ctypes
 import torch
 from . import _lib
-from ._dispatch import same_dtype, on_device, Batch, dtype_code, expand_batch, no_grad_required, require_gpu, stream_ptr, broadcast_shapes
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
 from .utils import ensure_list
 
 # default arithmetic of the QR sweeps of eig_sym: 'fast' or 'reference' (module docstring)
@@ -51,16 +50,12 @@ SWEEP_ARITHMETIC = 'reference'
 
 
 def _prep(*tensors):
-    tensors = [torch.as_tensor(t) for t in tensors]
-    dev = require_gpu(*tensors)
-    no_grad_required(*tensors)
-    dtype = tensors[0].dtype
-    for t in tensors[1:]:
-        dtype = torch.promote_types(dtype, t.dtype)
-    if dtype.is_complex:
-        raise TypeError('nitorch_fastmath_amd.qr supports real float32/float64 matrices only')
-    dtype_code(dtype)
-    return dev, dtype, same_dtype(tensors, dtype)
+    try:
+        return prepare(None, *tensors)
+    except TypeError:        # the dtype check: complex matrices get this module's own message
+        if any(torch.as_tensor(t).is_complex() for t in tensors):
+            raise TypeError('nitorch_fastmath_amd.qr supports real float32/float64 matrices only') from None
+        raise
 
 
 def _check_finite(check, *tensors):
@@ -86,12 +81,11 @@ def _dummy(batch, dtype, dev):
     return torch.empty((), dtype=dtype, device=dev).expand(tuple(batch))
 
 
-def _run(fn, args_before, batch, inputs, ncomp, dtype, dev, out):
-    """Collapse the batch of `inputs`, call `fn(*args_before, n_outer, n_inner, *operands, out_ptr, stream)`."""
+def _run(fn, scalars, batch, inputs, ncomp, dtype, dev, out, slots=None):
+    """Collapse the batch of `inputs`, call `fn(dtype, *scalars, n_outer, n_inner, *operands, out_ptr, stream)`."""
     b = Batch(batch, list(inputs) + [_dummy(batch, dtype, dev)], list(ncomp) + [0])
-    ops = [ctypes.byref(o) if o is not None else None for o in b.operands[:-1]]
-    with on_device(dev):
-        _lib.check(fn(*args_before, b.n_outer, b.n_inner, *ops, out.data_ptr(), stream_ptr(dev)))
+    b._copyback = None       # the stand-in is never written: nothing to copy back
+    launch(fn, dev, dtype, scalars, b, range(len(inputs)) if slots is None else slots, (out.data_ptr(),))
 
 
 def _unpack_reflectors(pack, n):
@@ -127,7 +121,7 @@ def eig_sym(a, compute_u=False, upper=True, inplace=False, check_finite=True, ma
     s : `(..., m) tensor`
     u : `(..., m, m) tensor`, optional
     """
-    from ._autograd import EigSymFn, needs_grad
+    from ._autograd import EigSymFn
     arithmetic = SWEEP_ARITHMETIC if arithmetic is None else arithmetic
     if arithmetic not in ('fast', 'reference'):
         raise ValueError(f"arithmetic must be 'fast' or 'reference', got {arithmetic!r}")
@@ -144,7 +138,7 @@ def eig_sym(a, compute_u=False, upper=True, inplace=False, check_finite=True, ma
     out = _packed(batch, n + (n * n if compute_u else 0), dtype, dev)
     L = _lib.lib()
     flags = (_lib.EIG_VECTORS if compute_u else 0) | (_lib.EIG_FAST if arithmetic == 'fast' else 0)
-    _run(L.nfm_qr_eig_sym, (dtype_code(dtype), n, int(bool(upper)), flags, int(max_iter), float(tol)),
+    _run(L.nfm_qr_eig_sym, (n, int(bool(upper)), flags, int(max_iter), float(tol)),
          batch, [a], [2], dtype, dev, out)
     if compute_u:
         return out[..., :n], out[..., n:].unflatten(-1, (n, n))
@@ -165,18 +159,11 @@ def rq_hessenberg(h, u=None, inplace=False, check_finite=True):
     n = h.shape[-1]
     batch = h.shape[:-2] if u is None else broadcast_shapes(h.shape[:-2], u.shape[:-2])
     out = _packed(batch, n * n * (2 if u is not None else 1), dtype, dev)
-    L = _lib.lib()
+    fn = _lib.lib().nfm_qr_rq_hessenberg
     if u is None:
-        b = Batch(batch, [expand_batch(batch, h, 2), _dummy(batch, dtype, dev)], [2, 0])
-        with on_device(dev):
-            _lib.check(L.nfm_qr_rq_hessenberg(dtype_code(dtype), n, 0, b.n_outer, b.n_inner,
-                                              ctypes.byref(b.operands[0]), None, out.data_ptr(), stream_ptr(dev)))
+        _run(fn, (n, 0), batch, [expand_batch(batch, h, 2)], [2], dtype, dev, out, slots=(0, None))
         return out.unflatten(-1, (n, n))
-    b = Batch(batch, [expand_batch(batch, h, 2), expand_batch(batch, u, 2), _dummy(batch, dtype, dev)], [2, 2, 0])
-    with on_device(dev):
-        _lib.check(L.nfm_qr_rq_hessenberg(dtype_code(dtype), n, 0, b.n_outer, b.n_inner,
-                                          ctypes.byref(b.operands[0]), ctypes.byref(b.operands[1]),
-                                          out.data_ptr(), stream_ptr(dev)))
+    _run(fn, (n, 0), batch, [expand_batch(batch, h, 2), expand_batch(batch, u, 2)], [2, 2], dtype, dev, out)
     out = out.unflatten(-1, (2, n, n))
     return out[..., 0, :, :], out[..., 1, :, :]
 
@@ -189,7 +176,7 @@ def qr_hessenberg(h, inplace=False, check_finite=True):
     n = h.shape[-1]
     batch = h.shape[:-2]
     out = _packed(batch, 2 * n * n, dtype, dev)
-    _run(_lib.lib().nfm_qr_qr_hessenberg, (dtype_code(dtype), n), batch, [h], [2], dtype, dev, out)
+    _run(_lib.lib().nfm_qr_qr_hessenberg, (n,), batch, [h], [2], dtype, dev, out)
     out = out.unflatten(-1, (2, n, n))
     return out[..., 0, :, :], out[..., 1, :, :]
 
@@ -202,7 +189,7 @@ def _hessenberg(a, sym, upper, with_u, check_finite):
     batch = a.shape[:-2]
     nu = max(n - 2, 0) * (n - 1) if with_u else 0
     out = _packed(batch, n * n + nu, dtype, dev)
-    _run(_lib.lib().nfm_qr_hessenberg, (dtype_code(dtype), n, int(sym), int(bool(upper)), int(bool(with_u))),
+    _run(_lib.lib().nfm_qr_hessenberg, (n, int(sym), int(bool(upper)), int(bool(with_u))),
          batch, [a], [2], dtype, dev, out)
     h = out[..., :n * n].unflatten(-1, (n, n))
     if with_u:
@@ -249,7 +236,7 @@ def householder(x, basis=0, inplace=False, check_finite=True, return_alpha=False
     basis = basis if basis >= 0 else n + basis
     batch = x.shape[:-1]
     out = _packed(batch, n + 1, dtype, dev)
-    _run(_lib.lib().nfm_qr_householder, (dtype_code(dtype), n, int(basis)), batch, [x], [1], dtype, dev, out)
+    _run(_lib.lib().nfm_qr_householder, (n, int(basis)), batch, [x], [1], dtype, dev, out)
     u, alpha = out[..., :n], out[..., n]
     return (u, alpha) if return_alpha else u
 
@@ -276,10 +263,7 @@ def householder_apply(a, u, k=None, side='both', inverse=False, inplace=False, c
     for uk in us:
         m = uk.shape[-1]
         b = Batch(batch, [expand_batch(batch, uk, 1), out], [1, 2])
-        with on_device(dev):
-            _lib.check(L.nfm_qr_householder_apply(dtype_code(dtype), n, m, _lib.SIDE[side.lower()], b.n_outer, b.n_inner,
-                                                  ctypes.byref(b.operands[1]), ctypes.byref(b.operands[0]),
-                                                  stream_ptr(dev)))
+        launch(L.nfm_qr_householder_apply, dev, dtype, (n, m, _lib.SIDE[side.lower()]), b, (1, 0))
     if inplace and out.shape == a.shape:
         a.copy_(out)
         return a
@@ -291,7 +275,7 @@ def givens(x, y):
     dev, dtype, (x, y) = _prep(x, y)
     batch = broadcast_shapes(x.shape, y.shape)
     out = _packed(batch, 2, dtype, dev)
-    _run(_lib.lib().nfm_qr_givens, (dtype_code(dtype),), batch,
+    _run(_lib.lib().nfm_qr_givens, (), batch,
          [expand_batch(batch, x, 0), expand_batch(batch, y, 0)], [0, 0], dtype, dev, out)
     return out[..., 0], out[..., 1]
 
@@ -314,11 +298,7 @@ def givens_apply(a, c, s, i=0, j=None, side='both', inplace=False, check_finite=
     batch = vshape[:-1]
     out = expand_batch(batch, a, 2).clone(memory_format=torch.contiguous_format)
     b = Batch(batch, [c.expand(vshape), s.expand(vshape), out], [1, 1, 2])
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_qr_givens_apply(dtype_code(dtype), n, _lib.SIDE[side.lower()], int(i), int(j),
-                                                  b.n_outer, b.n_inner, ctypes.byref(b.operands[2]),
-                                                  ctypes.byref(b.operands[0]), ctypes.byref(b.operands[1]),
-                                                  stream_ptr(dev)))
+    launch(_lib.lib().nfm_qr_givens_apply, dev, dtype, (n, _lib.SIDE[side.lower()], int(i), int(j)), b, (2, 0, 1))
     if inplace and out.shape == a.shape:
         a.copy_(out)
         return a

@@ -27,12 +27,8 @@ __all__ = [
 import builtins
 import torch
 from . import _lib
-from ._dispatch import on_device, dtype_code, no_grad_required, require_gpu, stream_ptr
+from ._dispatch import call, dtype_code, needs_grad, no_grad_required, require_gpu
 from .utils import ensure_list, ind2sub
-
-
-def _needs_grad(t):
-    return torch.is_grad_enabled() and t.requires_grad
 
 
 def _SumFn():
@@ -175,9 +171,7 @@ def _reduce(op, input, dim, keepdim, out_dtype, want_idx=False):
         x = input if input.is_contiguous() else input.contiguous()
         out = torch.empty([], dtype=out_dtype, device=dev)
         ws, wsn = _workspace(dev)
-        with on_device(dev):
-            _lib.check(L.nfm_reduce_all(code, op, ocode, x.numel(), x.data_ptr(), ws.data_ptr(), wsn,
-                                        out.data_ptr(), stream_ptr(dev)))
+        call(L.nfm_reduce_all, dev, code, op, ocode, x.numel(), x.data_ptr(), ws.data_ptr(), wsn, out.data_ptr())
         if keepdim:
             out = out.reshape([1] * nd)
         return out, None, None, None
@@ -189,10 +183,9 @@ def _reduce(op, input, dim, keepdim, out_dtype, want_idx=False):
     if red == 0 and op in (_lib.RED_NANMAX, _lib.RED_NANMIN, _lib.RED_MAX, _lib.RED_MIN):
         raise IndexError('cannot take the max/min over an empty dimension')
     ws, wsn = _workspace(dev, L.nfm_reduce_dim_workspace_bytes(code, op, outer, red, inner, int(want_idx)))
-    with on_device(dev):
-        _lib.check(L.nfm_reduce_dim(code, op, ocode, outer, red, inner, x.data_ptr(),
-                                    ws.data_ptr() if ws is not None else None, wsn, out.data_ptr(),
-                                    idx.data_ptr() if idx is not None else None, stream_ptr(dev)))
+    call(L.nfm_reduce_dim, dev, code, op, ocode, outer, red, inner, x.data_ptr(),
+         ws.data_ptr() if ws is not None else None, wsn, out.data_ptr(),
+         idx.data_ptr() if idx is not None else None)
     if keepdim:
         keptshape = [1 if d in dims else s for d, s in enumerate(shape)]
         out = out.reshape(keptshape)
@@ -255,14 +248,14 @@ def max(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_ind
     max(input) -> Tensor; max(input, dim) -> Tensor;
     max(input, dim, return_indices=True) -> (Tensor, Tensor)
     """
-    if _needs_grad(torch.as_tensor(input)):
+    if needs_grad(torch.as_tensor(input)):
         return _pick_with_grad('max', input, dim, keepdim, omitnan, return_indices, out)
     return _reduce_index(_lib.RED_MAX, _lib.RED_NANMAX, input, dim, keepdim, omitnan, return_indices, out)
 
 
 def min(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_indices=False, out=None):
     r"""Multi-dimensional min reduction (`reduce.py:200-252`)."""
-    if _needs_grad(torch.as_tensor(input)):
+    if needs_grad(torch.as_tensor(input)):
         return _pick_with_grad('min', input, dim, keepdim, omitnan, return_indices, out)
     return _reduce_index(_lib.RED_MIN, _lib.RED_NANMIN, input, dim, keepdim, omitnan, return_indices, out)
 
@@ -293,7 +286,7 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
     """
     input = torch.as_tensor(input)
     dev = require_gpu(input)
-    grad = _needs_grad(input)
+    grad = needs_grad(input)
     if grad and out is not None:
         raise RuntimeError('out= is not supported for tensors that require grad')
     code = dtype_code(input.dtype)
@@ -329,10 +322,8 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
     inner = _prod(input.shape[d0 + len(dims):])
     if (dims == list(range(d0, d0 + len(dims))) and inner > 1 and input.is_contiguous() and rows >= 4096
             and 2 <= red <= L.nfm_reduce_median_lane_max(code)):
-        with on_device(dev):
-            _lib.check(L.nfm_reduce_median_mid(code, int(bool(omitnan)), rows // inner, red, inner,
-                                               input.detach().data_ptr(), val.data_ptr(),
-                                               idx.data_ptr() if idx is not None else None, stream_ptr(dev)))
+        call(L.nfm_reduce_median_mid, dev, code, int(bool(omitnan)), rows // inner, red, inner,
+             input.detach().data_ptr(), val.data_ptr(), idx.data_ptr() if idx is not None else None)
         rows_done = True
     else:
         rows_done = False
@@ -347,10 +338,9 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
     for lo in ([] if rows_done else range(0, rows, builtins.max(step, 1))):
         hi = builtins.min(rows, lo + step)
         ws, wsn = _workspace(dev, L.nfm_reduce_median_workspace_bytes(hi - lo, red))
-        with on_device(dev):
-            _lib.check(L.nfm_reduce_median(code, int(bool(omitnan)), hi - lo, red, x[lo:hi].data_ptr(),
-                                           ws.data_ptr() if ws is not None else None, wsn, val[lo:hi].data_ptr(),
-                                           idx[lo:hi].data_ptr() if idx is not None else None, stream_ptr(dev)))
+        call(L.nfm_reduce_median, dev, code, int(bool(omitnan)), hi - lo, red, x[lo:hi].data_ptr(),
+             ws.data_ptr() if ws is not None else None, wsn, val[lo:hi].data_ptr(),
+             idx[lo:hi].data_ptr() if idx is not None else None)
     if grad:      # the gradient goes to the selected element: pick it out of the differentiable rows
         val = xg.gather(1, idx[:, None])[:, 0]
     shape = [1 if d in dims else s for d, s in enumerate(input.shape)] if keepdim else subshape
@@ -371,7 +361,7 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
 def sum(input, dim=None, keepdim=False, omitnan=False, inplace=False, dtype=None, out=None):
     """Sum of a tensor (`reduce.py:431-468`); `dtype` is the accumulator/output dtype."""
     input = torch.as_tensor(input)
-    if _needs_grad(input):
+    if needs_grad(input):
         return _deliver(_SumFn().apply(input, dim, keepdim, omitnan, False, dtype), out)
     op = _lib.RED_NANSUM if omitnan else _lib.RED_SUM
     val, _, _, _ = _reduce(op, input, dim, keepdim, dtype or input.dtype)
@@ -395,10 +385,8 @@ def _moments(input, dim, keepdim):
     subshape = [shape[d] for d in kept]
     out = torch.zeros(subshape + [4], dtype=torch.float64, device=dev)
     ws, wsn = _workspace(dev, L.nfm_reduce_moments_workspace_bytes(code, outer, red, inner))
-    with on_device(dev):
-        _lib.check(L.nfm_reduce_moments(code, outer, red, inner, x.data_ptr(),
-                                        ws.data_ptr() if ws is not None else None, wsn,
-                                        out.data_ptr(), stream_ptr(dev)))
+    call(L.nfm_reduce_moments, dev, code, outer, red, inner, x.data_ptr(),
+         ws.data_ptr() if ws is not None else None, wsn, out.data_ptr())
     if keepdim:
         out = out.reshape([1 if d in dims else s for d, s in enumerate(shape)] + [4])
     return out[..., 0], out[..., 1], out[..., 2], out[..., 3], red
@@ -466,10 +454,8 @@ def _stat(kind, input, dim, keepdim, omitnan, unbiased, out_dtype):
         out.fill_(float('nan'))
     stat = kind | (_STAT_OMITNAN if omitnan else 0) | (_STAT_UNBIASED if unbiased else 0)
     ws, wsn = _workspace(dev, L.nfm_reduce_moments_workspace_bytes(code, outer, red, inner))
-    with on_device(dev):
-        _lib.check(L.nfm_reduce_stat(code, stat, ocode, outer, red, inner, x.data_ptr(),
-                                     ws.data_ptr() if ws is not None else None, wsn,
-                                     out.data_ptr(), stream_ptr(dev)))
+    call(L.nfm_reduce_stat, dev, code, stat, ocode, outer, red, inner, x.data_ptr(),
+         ws.data_ptr() if ws is not None else None, wsn, out.data_ptr())
     if keepdim:
         out = out.reshape([1 if d in dims else s for d, s in enumerate(shape)])
     return out
@@ -478,7 +464,7 @@ def _stat(kind, input, dim, keepdim, omitnan, unbiased, out_dtype):
 def mean(input, dim=None, keepdim=False, omitnan=False, inplace=False, dtype=None, out=None):
     """Mean of a tensor (`reduce.py:513-550`)."""
     input = torch.as_tensor(input)
-    if _needs_grad(input):
+    if needs_grad(input):
         return _deliver(_SumFn().apply(input, dim, keepdim, omitnan, True, dtype), out)
     return _deliver(_stat(_STAT_MEAN, input, dim, keepdim, omitnan, False, dtype or input.dtype), out)
 
@@ -491,7 +477,7 @@ def nanmean(input, dim=None, keepdim=False, inplace=False, dtype=None, out=None)
 def var(input, dim=None, keepdim=False, unbiased=True, omitnan=False, inplace=False, dtype=None, out=None):
     """Variance of a tensor (`reduce.py:597-635`; the non-NaN form raises upstream, quirk Q13)."""
     input = torch.as_tensor(input)
-    if _needs_grad(input):
+    if needs_grad(input):
         from ._autograd import VarFn
         return _deliver(VarFn.apply(input, dim, keepdim, unbiased, omitnan, False, dtype), out)
     return _deliver(_stat(_STAT_VAR, input, dim, keepdim, omitnan, unbiased, dtype or input.dtype), out)
@@ -505,7 +491,7 @@ def nanvar(input, dim=None, keepdim=False, unbiased=True, inplace=False, dtype=N
 def std(input, dim=None, keepdim=False, unbiased=True, omitnan=False, inplace=False, dtype=None, out=None):
     """Standard deviation of a tensor (`reduce.py:688-726`)."""
     input = torch.as_tensor(input)
-    if _needs_grad(input):
+    if needs_grad(input):
         from ._autograd import VarFn
         return _deliver(VarFn.apply(input, dim, keepdim, unbiased, omitnan, True, dtype), out)
     return _deliver(_stat(_STAT_STD, input, dim, keepdim, omitnan, unbiased, dtype or input.dtype), out)

@@ -22,15 +22,11 @@ saved input; the K > 48 route is torch ops, differentiated by torch.
 __all__ = ['logsumexp', 'softmax', 'log_softmax', 'logit', 'softmax_lse']
 import torch
 from . import _lib
-from ._dispatch import on_device, dtype_code, require_gpu, stream_ptr
+from ._dispatch import call, dtype_code, needs_grad, require_gpu
 from .utils import ensure_list
 
 MAX_K = _lib.SX_MAX_K      # stored classes K served by the kernels (include/nfm_hip.h: NFM_SIMPLEX_MAX_K)
 REGISTER_MAX_KP = 17       # ... with the classes in registers: K' = K + (implicit input) up to this
-
-
-def _needs_grad(t):
-    return torch.is_grad_enabled() and t.requires_grad
 
 
 def _pair(implicit):
@@ -149,11 +145,9 @@ def _forward(op, x, d, imp_in, imp_out, idx, want_lse=False):
         if lse is None:
             return out, lse
         op, imp_out, only_lse = _lib.SX_LOGSUMEXP, False, True
-    dev = x.device
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_simplex_forward(
-            dtype_code(x.dtype), op, _flags(imp_in, imp_out), idx, outer, K, inner, x.data_ptr(),
-            None if only_lse else out.data_ptr(), None if lse is None else lse.data_ptr(), stream_ptr(dev)))
+    call(_lib.lib().nfm_simplex_forward, x.device,
+         dtype_code(x.dtype), op, _flags(imp_in, imp_out), idx, outer, K, inner, x.data_ptr(),
+         None if only_lse else out.data_ptr(), None if lse is None else lse.data_ptr())
     return out, lse
 
 
@@ -167,11 +161,9 @@ def _backward(op, saved, g, d, K, imp_in, imp_out, idx):
         return grad
     if K + imp_in - imp_out == 0:       # the output had no classes
         return grad.zero_()
-    dev = saved.device
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_simplex_backward(
-            dtype_code(saved.dtype), op, _flags(imp_in, imp_out), idx, outer, K, inner, saved.data_ptr(),
-            g.data_ptr(), grad.data_ptr(), stream_ptr(dev)))
+    call(_lib.lib().nfm_simplex_backward, saved.device,
+         dtype_code(saved.dtype), op, _flags(imp_in, imp_out), idx, outer, K, inner, saved.data_ptr(),
+         g.data_ptr(), grad.data_ptr())
     return grad
 
 
@@ -181,7 +173,7 @@ def _run(op, input, dim, implicit, implicit_index):
     x, d, restore = _prepare(input, dim)
     K = x.shape[d]
     idx = _index(implicit_index, K + imp_in)
-    if _needs_grad(x):
+    if needs_grad(x):
         if K > MAX_K:
             return restore(_torch_forward(op, x, d, imp_in, imp_out, idx)[0])
         from . import _autograd
@@ -204,7 +196,7 @@ def logsumexp(input, dim=-1, keepdim=False, implicit=False):
     imp_in = bool(implicit)
     x, d, restore = _prepare(input, dim)
     K = x.shape[d]
-    if _needs_grad(x):
+    if needs_grad(x):
         if K > MAX_K:
             lse = _torch_forward(_lib.SX_LOGSUMEXP, x, d, imp_in, False, K if imp_in else 0)[1]
         else:
@@ -261,7 +253,7 @@ def softmax_lse(input, dim=-1, weights=None, implicit=False):
     x, d, restore = _prepare(input, dim)
     K = x.shape[d]
     idx = K + imp_in - 1
-    if _needs_grad(x):
+    if needs_grad(x):
         p = softmax(input, dim, (imp_in, imp_out), -1)
         lse = logsumexp(input, dim, keepdim=True, implicit=imp_in)
     else:

@@ -14,14 +14,10 @@ __all__ = ['mvdigamma', 'besseli', 'besseli_ratio']
 import math
 import torch
 from . import _lib
-from ._dispatch import on_device, dtype_code, require_gpu, stream_ptr
+from ._dispatch import call, dtype_code, needs_grad, require_gpu
 
 MAX_N = _lib.SP_MAX_N      # besseli_ratio: rounds N served by the kernel (include/nfm_hip.h: NFM_SPECIAL_MAX_N)
 _MODES = {None: 0, 0: 0, 1: 1, 2: 2, 'norm': 1, 'log': 2}
-
-
-def _needs_grad(t):
-    return torch.is_grad_enabled() and t.requires_grad
 
 
 def _dense(t):
@@ -58,17 +54,10 @@ def _nu(nu):
     return nu
 
 
-def _call(fn, like, *args):
-    """run one C-ABI entry point on the stream of `like`'s device"""
-    dev = like.device
-    with on_device(dev):
-        _lib.check(fn(*args, stream_ptr(dev)))
-
-
 def _besseli_forward(nu, z, code):
     out = _like(z)
     if z.numel():
-        _call(_lib.lib().nfm_special_besseli, z, dtype_code(z.dtype), code, nu, z.numel(), z.data_ptr(), out.data_ptr())
+        call(_lib.lib().nfm_special_besseli, z.device, dtype_code(z.dtype), code, nu, z.numel(), z.data_ptr(), out.data_ptr())
     return out
 
 
@@ -78,8 +67,8 @@ def _besseli_backward(nu, z, out, g, code):
         g = _like(z).copy_(g)
     grad = _like(z)
     if z.numel():
-        _call(_lib.lib().nfm_special_besseli_backward, z, dtype_code(z.dtype), code, nu, z.numel(), z.data_ptr(),
-              out.data_ptr(), g.data_ptr(), grad.data_ptr())
+        call(_lib.lib().nfm_special_besseli_backward, z.device, dtype_code(z.dtype), code, nu, z.numel(), z.data_ptr(),
+             out.data_ptr(), g.data_ptr(), grad.data_ptr())
     return grad
 
 
@@ -91,7 +80,7 @@ def _ratio_forward(nu, x, N, K):
         return r if r.stride() == x.stride() else _like(x).copy_(r)
     out = _like(x)
     if x.numel():
-        _call(_lib.lib().nfm_special_besseli_ratio, x, dtype_code(x.dtype), nu, N, K, x.numel(), x.data_ptr(), out.data_ptr())
+        call(_lib.lib().nfm_special_besseli_ratio, x.device, dtype_code(x.dtype), nu, N, K, x.numel(), x.data_ptr(), out.data_ptr())
     return out
 
 
@@ -101,8 +90,8 @@ def _ratio_backward(nu, x, out, g):
         g = _like(x).copy_(g)
     grad = _like(x)
     if x.numel():
-        _call(_lib.lib().nfm_special_besseli_ratio_backward, x, dtype_code(x.dtype), nu, x.numel(), x.data_ptr(),
-              out.data_ptr(), g.data_ptr(), grad.data_ptr())
+        call(_lib.lib().nfm_special_besseli_ratio_backward, x.device, dtype_code(x.dtype), nu, x.numel(), x.data_ptr(),
+             out.data_ptr(), g.data_ptr(), grad.data_ptr())
     return grad
 
 
@@ -126,7 +115,7 @@ def _ratio_torch(nu, X, N, K):
 def _digamma_forward(x, order):
     out = _like(x)
     if x.numel():
-        _call(_lib.lib().nfm_special_mvdigamma, x, dtype_code(x.dtype), order, x.numel(), x.data_ptr(), out.data_ptr())
+        call(_lib.lib().nfm_special_mvdigamma, x.device, dtype_code(x.dtype), order, x.numel(), x.data_ptr(), out.data_ptr())
     return out
 
 
@@ -136,8 +125,8 @@ def _digamma_backward(x, g, order):
         g = _like(x).copy_(g)
     grad = _like(x)
     if x.numel():
-        _call(_lib.lib().nfm_special_mvdigamma_backward, x, dtype_code(x.dtype), order, x.numel(), x.data_ptr(),
-              g.data_ptr(), grad.data_ptr())
+        call(_lib.lib().nfm_special_mvdigamma_backward, x.device, dtype_code(x.dtype), order, x.numel(), x.data_ptr(),
+             g.data_ptr(), grad.data_ptr())
     return grad
 
 
@@ -152,7 +141,7 @@ def mvdigamma(input, order=1):
     if order < 1:
         raise ValueError(f'order must be >= 1, got {order}')
     x = _prepare('mvdigamma', input)
-    if _needs_grad(x):
+    if needs_grad(x):
         from . import _autograd
         return _autograd.MvDigammaFn.apply(x, order)
     return _digamma_forward(x, order)
@@ -177,7 +166,7 @@ def besseli(nu, z, mode=None):
         raise ValueError(f"mode must be one of None, 0, 1, 'norm', 2, 'log'; got {mode!r}") from None
     nu = _nu(nu)
     z = _prepare('besseli', z)
-    if _needs_grad(z):
+    if needs_grad(z):
         from . import _autograd
         return _autograd.BesseliFn.apply(z, nu, code)
     return _besseli_forward(nu, z, code)
@@ -196,7 +185,7 @@ def besseli_ratio(nu, X, N=4, K=10):
     if N < 0 or K < 0:
         raise ValueError(f'N and K must be >= 0, got N={N}, K={K}')
     X = _prepare('besseli_ratio', X)
-    if _needs_grad(X):
+    if needs_grad(X):
         from . import _autograd
         return _autograd.BesseliRatioFn.apply(X, nu, N, K)
     return _ratio_forward(nu, X, N, K)

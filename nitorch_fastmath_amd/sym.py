@@ -29,8 +29,7 @@ import ctypes
 from math import sqrt
 import torch
 from . import _lib
-from ._dispatch import (same_dtype, on_device, Batch, broadcast_shapes, common_dtype, dtype_code, expand_batch, no_grad_required,
-                        require_gpu, stream_ptr)
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
 
 
 def _nb_prm(K):
@@ -70,13 +69,15 @@ def _pivoting(pivoting):
     return mode == 'always'
 
 
-def _prep(dtype, *tensors):
-    tensors = [None if t is None else torch.as_tensor(t) for t in tensors]
-    dev = require_gpu(*tensors)
-    no_grad_required(*tensors)
-    dtype = common_dtype(dtype, *tensors)
-    dtype_code(dtype)
-    return dev, dtype, same_dtype(tensors, dtype)
+def _eps_array(eps, N):
+    """the `eps` argument of the C ABI: MAX_DIM doubles, the last given value repeated up to N (None: NULL)"""
+    if eps is None:
+        return None
+    e = [float(x) for x in torch.as_tensor(eps, dtype=torch.float64).flatten().tolist()]
+    if not e:
+        raise ValueError('eps is empty')
+    e = (e + [e[-1]] * N)[:N]
+    return (ctypes.c_double * _lib.MAX_DIM)(*(e + [0.0] * (_lib.MAX_DIM - N)))
 
 
 def _alloc_out(out, shape, dtype, device, like=None):
@@ -105,7 +106,7 @@ def _full_view(mat, N, kind):
 
 
 def _matvec_impl(mode, inp, mat, vec, dtype, out):
-    dev, dtype, (inp, mat, vec) = _prep(dtype, inp, mat, vec)
+    dev, dtype, (inp, mat, vec) = prepare(dtype, inp, mat, vec)
     N = vec.shape[-1]
     kind = _mat_kind(mat.shape[-1], N)
     if N > _lib.MAX_DIM:          # the reference's own large-order route, on the device (_bigorder.py)
@@ -125,13 +126,7 @@ def _matvec_impl(mode, inp, mat, vec, dtype, out):
     ops.append(out)
     ncs.append(1)
     b = Batch(batch, ops, ncs, pack=N > 8 and kind == _lib.MAT_SYM)
-    o = b.operands
-    o_inp = ctypes.byref(o[2]) if inp is not None else None
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_matvec(
-            dtype_code(dtype), N, kind, mode, b.n_outer, b.n_inner, ctypes.byref(o[0]),
-            ctypes.byref(o[1]), o_inp, ctypes.byref(o[-1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_matvec, dev, dtype, (N, kind, mode), b, (0, 1, None if inp is None else 2, -1))
     return out
 
 
@@ -147,7 +142,7 @@ def _cast(dtype, *tensors):
 
 
 def _matvec(mode, inp, mat, vec, dtype, out):
-    from ._autograd import SymMatvecFn, needs_grad
+    from ._autograd import SymMatvecFn
     if needs_grad(inp, mat, vec):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -232,7 +227,7 @@ def sym_solve(mat, vec, eps=None, dtype=None, out=None, *, pivoting=None):
     -------
     result : `(..., M) tensor`
     """
-    from ._autograd import SymSolveFn, needs_grad
+    from ._autograd import SymSolveFn
     if needs_grad(mat, vec):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -241,7 +236,7 @@ def sym_solve(mat, vec, eps=None, dtype=None, out=None, *, pivoting=None):
             mat_, vec_ = _cast(dtype, mat, vec)
             return _bigorder.sym_solve(mat_, vec_, eps, None, mat_.shape[-1])
         return SymSolveFn.apply(torch.as_tensor(mat), torch.as_tensor(vec), eps, dtype)
-    dev, dtype, (mat, vec) = _prep(dtype, mat, vec)
+    dev, dtype, (mat, vec) = prepare(dtype, mat, vec)
     N = vec.shape[-1]
     kind = _mat_kind(mat.shape[-1], N)
     if N > _lib.MAX_DIM:          # densify + torch.linalg.solve on the device, as `_impl/sym.py:392-396`
@@ -256,19 +251,8 @@ def sym_solve(mat, vec, eps=None, dtype=None, out=None, *, pivoting=None):
                         like=vec if (N <= 8 or (kind == _lib.MAT_SYM and not piv)) else None)
     b = Batch(batch, [expand_batch(batch, matv, mat_nc), expand_batch(batch, vec, 1), out], [mat_nc, 1, 1],
               pack=('all' if piv else True) if (N > 8 and kind == _lib.MAT_SYM) else False)
-    o = b.operands
-    eps_p = None
-    if eps is not None:
-        e = [float(x) for x in torch.as_tensor(eps, dtype=torch.float64).flatten().tolist()]
-        if not e:
-            raise ValueError('eps is empty')
-        e = (e + [e[-1]] * N)[:N]
-        eps_p = (ctypes.c_double * _lib.MAX_DIM)(*(e + [0.0] * (_lib.MAX_DIM - N)))
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_solve(
-            dtype_code(dtype), N, kind | (_lib.MAT_PIVOTED if piv else 0), b.n_outer, b.n_inner, ctypes.byref(o[0]),
-            ctypes.byref(o[1]), ctypes.byref(o[2]), eps_p, stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_solve, dev, dtype, (N, kind | (_lib.MAT_PIVOTED if piv else 0)), b,
+           tail=(_eps_array(eps, N),))
     return out
 
 
@@ -291,7 +275,7 @@ def sym_invert(mat, diag=False, dtype=None, out=None, *, pivoting=None):
         If True, only return the diagonal of the inverse, shape `(..., M)`.
     pivoting : {'auto', 'always'}, keyword-only: see `sym_solve`.
     """
-    from ._autograd import SymInvertFn, needs_grad
+    from ._autograd import SymInvertFn
     if needs_grad(mat):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -300,7 +284,7 @@ def sym_invert(mat, diag=False, dtype=None, out=None, *, pivoting=None):
             (mat_,) = _cast(dtype, mat)
             return _bigorder.sym_invert(mat_, _nb_prm(mat_.shape[-1]), bool(diag), None)
         return SymInvertFn.apply(torch.as_tensor(mat), bool(diag), dtype)
-    dev, dtype, (mat,) = _prep(dtype, mat)
+    dev, dtype, (mat,) = prepare(dtype, mat)
     M = _nb_prm(mat.shape[-1])
     if M > _lib.MAX_DIM:
         from . import _bigorder
@@ -310,12 +294,7 @@ def sym_invert(mat, diag=False, dtype=None, out=None, *, pivoting=None):
     uncovered = piv          # (the pivoted kernels of orders 9..16 want contiguous records: everything is packed for them)
     out, _ = _alloc_out(out, tuple(batch) + ((M,) if diag else (mat.shape[-1],)), dtype, dev, like=None if uncovered else mat)
     b = Batch(batch, [mat, out], [1, 1], pack=('all' if uncovered else True) if (M > 8 and not diag) else False)
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_invert(
-            dtype_code(dtype), M, int(bool(diag)) | (_lib.INVERT_PIVOTED if piv else 0), b.n_outer, b.n_inner, ctypes.byref(o[0]),
-            ctypes.byref(o[1]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_invert, dev, dtype, (M, int(bool(diag)) | (_lib.INVERT_PIVOTED if piv else 0)), b)
     return out
 
 
@@ -330,7 +309,7 @@ def sym_det(mat, dtype=None, out=None):
     The reference derives M from a batch dimension by mistake (quirk Q2); this
     implementation uses the compact dimension, as documented.
     """
-    from ._autograd import SymDetFn, needs_grad
+    from ._autograd import SymDetFn
     if needs_grad(mat):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -339,7 +318,7 @@ def sym_det(mat, dtype=None, out=None):
             (mat_,) = _cast(dtype, mat)
             return _bigorder.sym_det(mat_, _nb_prm(mat_.shape[-1]), None)
         return SymDetFn.apply(torch.as_tensor(mat), dtype)
-    dev, dtype, (mat,) = _prep(dtype, mat)
+    dev, dtype, (mat,) = prepare(dtype, mat)
     M = _nb_prm(mat.shape[-1])
     if M > _lib.MAX_DIM:
         from . import _bigorder
@@ -347,12 +326,7 @@ def sym_det(mat, dtype=None, out=None):
     batch = mat.shape[:-1]
     out, _ = _alloc_out(out, tuple(batch), dtype, dev)
     b = Batch(batch, [mat, out], [1, 0], pack=M > 8)
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_det(
-            dtype_code(dtype), M, b.n_outer, b.n_inner, ctypes.byref(o[0]), ctypes.byref(o[1]),
-            stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_det, dev, dtype, (M,), b)
     return out
 
 
@@ -363,11 +337,11 @@ def _grad_guard(out):
 
 def sym_to_full(mat, dtype=None, out=None):
     r"""Compact symmetric `(..., M*(M+1)//2)` -> full `(..., M, M)` (`_impl/sym.py:16-60`)."""
-    from ._autograd import SymToFullFn, needs_grad
+    from ._autograd import SymToFullFn
     if needs_grad(mat):
         _grad_guard(out)
         return SymToFullFn.apply(torch.as_tensor(mat), dtype)
-    dev, dtype, (mat,) = _prep(dtype, mat)
+    dev, dtype, (mat,) = prepare(dtype, mat)
     M = _nb_prm(mat.shape[-1])
     if M > _lib.MAX_DIM:
         from . import _bigorder
@@ -375,12 +349,7 @@ def sym_to_full(mat, dtype=None, out=None):
     batch = mat.shape[:-1]
     out, _ = _alloc_out(out, tuple(batch) + (M, M), dtype, dev)
     b = Batch(batch, [mat, out], [1, 2])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_to_full(
-            dtype_code(dtype), M, b.n_outer, b.n_inner, ctypes.byref(o[0]), ctypes.byref(o[1]),
-            stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_to_full, dev, dtype, (M,), b)
     return out
 
 
@@ -393,22 +362,17 @@ def sym_diag(mat):
 
 def sym_outer(x, dtype=None, out=None):
     r"""Symmetric outer product `x x^T` in compact storage (`_impl/sym.py:496-528`)."""
-    from ._autograd import SymOuterFn, needs_grad
+    from ._autograd import SymOuterFn
     if needs_grad(x):
         _grad_guard(out)
         return SymOuterFn.apply(torch.as_tensor(x), dtype)
-    dev, dtype, (x,) = _prep(dtype, x)
+    dev, dtype, (x,) = prepare(dtype, x)
     M = x.shape[-1]
     _check_order(M)
     batch = x.shape[:-1]
     out, _ = _alloc_out(out, tuple(batch) + (M * (M + 1) // 2,), dtype, dev)
     b = Batch(batch, [x, out], [1, 1])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_outer(
-            dtype_code(dtype), M, b.n_outer, b.n_inner, ctypes.byref(o[0]), ctypes.byref(o[1]),
-            stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_outer, dev, dtype, (M,), b)
     return out
 
 
@@ -419,11 +383,11 @@ def sym_matmul(j, h, dtype=None, out=None):
     For `k == d` in `{2, 3}` the reference's specialised kernels evaluate `J H J^T`
     (quirk Q16); this function returns what the reference returns.
     """
-    from ._autograd import SymMatmulFn, needs_grad
+    from ._autograd import SymMatmulFn
     if needs_grad(j, h):
         _grad_guard(out)
         return SymMatmulFn.apply(torch.as_tensor(j), torch.as_tensor(h), dtype)
-    dev, dtype, (j, h) = _prep(dtype, j, h)
+    dev, dtype, (j, h) = prepare(dtype, j, h)
     k, d = j.shape[-2:]
     _check_order(k)
     _check_order(d)
@@ -436,12 +400,7 @@ def sym_matmul(j, h, dtype=None, out=None):
     batch = broadcast_shapes(j.shape[:-2], h.shape[:-1])
     out, _ = _alloc_out(out, tuple(batch) + (d * (d + 1) // 2,), dtype, dev)
     b = Batch(batch, [expand_batch(batch, j, 2), expand_batch(batch, h, 1), out], [2, 1, 1])
-    o = b.operands
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_matmul(
-            dtype_code(dtype), k, d, hk, b.n_outer, b.n_inner, ctypes.byref(o[0]), ctypes.byref(o[1]),
-            ctypes.byref(o[2]), stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_matmul, dev, dtype, (k, d, hk), b)
     return out
 
 
@@ -456,11 +415,10 @@ def sym_matmul_solve(j, h, g, eps=None, dtype=None, out=None):
 
     j : `(..., k, d)`, h : `(..., k*(k+1)//2)` or `(..., k)`, g : `(..., d)` -> `(..., d)`.
     """
-    from ._autograd import needs_grad
     k, d = torch.as_tensor(j).shape[-2:]
     if needs_grad(j, h, g) or k > 4 or d > 4:
         return sym_solve(sym_matmul(j, h, dtype=dtype), g, eps=eps, dtype=dtype, out=out)
-    dev, dtype, (j, h, g) = _prep(dtype, j, h, g)
+    dev, dtype, (j, h, g) = prepare(dtype, j, h, g)
     if h.shape[-1] == k * (k + 1) // 2:
         hk = _lib.MAT_SYM
     elif h.shape[-1] == k:
@@ -473,17 +431,5 @@ def sym_matmul_solve(j, h, g, eps=None, dtype=None, out=None):
     out, _ = _alloc_out(out, tuple(batch) + (d,), dtype, dev, like=g)
     b = Batch(batch, [expand_batch(batch, j, 2), expand_batch(batch, h, 1), expand_batch(batch, g, 1), out],
               [2, 1, 1, 1])
-    o = b.operands
-    eps_p = None
-    if eps is not None:
-        e = [float(x) for x in torch.as_tensor(eps, dtype=torch.float64).flatten().tolist()]
-        if not e:
-            raise ValueError('eps is empty')
-        e = (e + [e[-1]] * d)[:d]
-        eps_p = (ctypes.c_double * _lib.MAX_DIM)(*(e + [0.0] * (_lib.MAX_DIM - d)))
-    with on_device(dev):
-        _lib.check(_lib.lib().nfm_sym_matmul_solve(
-            dtype_code(dtype), k, d, hk, b.n_outer, b.n_inner, ctypes.byref(o[0]), ctypes.byref(o[1]),
-            ctypes.byref(o[2]), ctypes.byref(o[3]), eps_p, stream_ptr(dev)))
-    b.finish()
+    launch(_lib.lib().nfm_sym_matmul_solve, dev, dtype, (k, d, hk), b, tail=(_eps_array(eps, d),))
     return out
