@@ -90,9 +90,10 @@ class SymMatvecFn(torch.autograd.Function):
 
 class SymSolveFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mat, vec, eps, dtype):
+    def forward(ctx, mat, vec, eps, dtype, pivoting=None):
         from . import sym
-        x = sym.sym_solve(mat, vec, eps=eps, dtype=dtype)
+        x = sym.sym_solve(mat, vec, eps=eps, dtype=dtype, pivoting=pivoting)
+        ctx.pivoting = pivoting
         ctx.kind = sym._mat_kind(mat.shape[-1], vec.shape[-1])
         ctx.eps = eps
         ctx.shapes = (mat.shape, vec.shape)
@@ -108,13 +109,13 @@ class SymSolveFn(torch.autograd.Function):
         N = x.shape[-1]
         g = g.contiguous()
         # x = A^-1 v  =>  v_bar = A^-T g,  A_bar = -v_bar x^T
-        gv = sym.sym_solve(_transposed(mat.to(g.dtype), ctx.kind, N), g, eps=ctx.eps)
+        gv = sym.sym_solve(_transposed(mat.to(g.dtype), ctx.kind, N), g, eps=ctx.eps, pivoting=ctx.pivoting)
         g_mat = g_vec = None
         if ctx.needs_input_grad[0]:
             g_mat = _sum_to(_mat_cotangent(ctx.kind, gv, x, True), ctx.shapes[0]).to(ctx.dtypes[0])
         if ctx.needs_input_grad[1]:
             g_vec = _sum_to(gv, ctx.shapes[1]).to(ctx.dtypes[1])
-        return g_mat, g_vec, None, None
+        return g_mat, g_vec, None, None, None
 
 
 class EigSymFn(torch.autograd.Function):
@@ -292,10 +293,10 @@ class SymInvertFn(torch.autograd.Function):
     """compact B = A^-1 (or its diagonal): full cotangent -B G B pulled back onto compact storage."""
 
     @staticmethod
-    def forward(ctx, mat, diag, dtype):
+    def forward(ctx, mat, diag, dtype, pivoting=None):
         from . import sym as S
         with torch.no_grad():
-            inv = S.sym_invert(mat, dtype=dtype)
+            inv = S.sym_invert(mat, dtype=dtype, pivoting=pivoting)
         ctx.save_for_backward(inv)
         ctx.diag = diag
         ctx.in_dtype = mat.dtype
@@ -313,7 +314,7 @@ class SymInvertFn(torch.autograd.Function):
             # the compact cotangent counts an off-diagonal entry once: split it over (i, j) and (j, i)
             Gf = (Gf + torch.diag_embed(Gf.diagonal(dim1=-2, dim2=-1))) / 2
         full = -_small_matmul(_small_matmul(Bf, Gf), Bf)
-        return _full_to_compact_grad(full).to(ctx.in_dtype), None, None
+        return _full_to_compact_grad(full).to(ctx.in_dtype), None, None, None
 
 
 class SymDetFn(torch.autograd.Function):

@@ -228,6 +228,7 @@ def sym_solve(mat, vec, eps=None, dtype=None, out=None, *, pivoting=None):
     result : `(..., M) tensor`
     """
     from ._autograd import SymSolveFn
+    piv = _pivoting(pivoting)
     if needs_grad(mat, vec):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -235,7 +236,7 @@ def sym_solve(mat, vec, eps=None, dtype=None, out=None, *, pivoting=None):
             from . import _bigorder
             mat_, vec_ = _cast(dtype, mat, vec)
             return _bigorder.sym_solve(mat_, vec_, eps, None, mat_.shape[-1])
-        return SymSolveFn.apply(torch.as_tensor(mat), torch.as_tensor(vec), eps, dtype)
+        return SymSolveFn.apply(torch.as_tensor(mat), torch.as_tensor(vec), eps, dtype, 'always' if piv else 'auto')
     dev, dtype, (mat, vec) = prepare(dtype, mat, vec)
     N = vec.shape[-1]
     kind = _mat_kind(mat.shape[-1], N)
@@ -276,6 +277,7 @@ def sym_invert(mat, diag=False, dtype=None, out=None, *, pivoting=None):
     pivoting : {'auto', 'always'}, keyword-only: see `sym_solve`.
     """
     from ._autograd import SymInvertFn
+    piv = _pivoting(pivoting)
     if needs_grad(mat):
         if out is not None:
             raise RuntimeError('out= is not supported for tensors that require grad')
@@ -283,14 +285,13 @@ def sym_invert(mat, diag=False, dtype=None, out=None, *, pivoting=None):
             from . import _bigorder
             (mat_,) = _cast(dtype, mat)
             return _bigorder.sym_invert(mat_, _nb_prm(mat_.shape[-1]), bool(diag), None)
-        return SymInvertFn.apply(torch.as_tensor(mat), bool(diag), dtype)
+        return SymInvertFn.apply(torch.as_tensor(mat), bool(diag), dtype, 'always' if piv else 'auto')
     dev, dtype, (mat,) = prepare(dtype, mat)
     M = _nb_prm(mat.shape[-1])
     if M > _lib.MAX_DIM:
         from . import _bigorder
         return _bigorder.sym_invert(mat, M, bool(diag), out)
     batch = mat.shape[:-1]
-    piv = _pivoting(pivoting)
     uncovered = piv          # (the pivoted kernels of orders 9..16 want contiguous records: everything is packed for them)
     out, _ = _alloc_out(out, tuple(batch) + ((M,) if diag else (mat.shape[-1],)), dtype, dev, like=None if uncovered else mat)
     b = Batch(batch, [mat, out], [1, 1], pack=('all' if uncovered else True) if (M > 8 and not diag) else False)
