@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 from conftest import TOL, EPS, relerr
+from _solver_ref import per_matrix_err
 
 pytestmark = pytest.mark.gpu
 
@@ -45,12 +46,6 @@ def test_sym_large_orders(dev, oracle, dn, M):
     ms = t(mat, dev).t().contiguous().t()
     assert relerr(S.sym_solve(ms, t(vec, dev)).cpu().numpy(), oracle.sym_solve(mat, vec)) <= TOL[dn]
     assert relerr(S.sym_invert(ms).cpu().numpy(), oracle.sym_invert(mat)) <= TOL[dn]
-
-
-def per_matrix_err(x, truth):
-    """max-norm relative error of every matrix of the batch against its own truth"""
-    x, truth = x.astype(np.float64).reshape(len(x), -1), truth.astype(np.float64).reshape(len(truth), -1)
-    return np.abs(x - truth).max(-1) / np.maximum(np.abs(truth).max(-1), 1e-300)
 
 
 @pytest.mark.parametrize('dn', ['f32', 'f64'])
