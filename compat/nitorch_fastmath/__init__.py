@@ -1,14 +1,16 @@
 """Import-compatible facade: put `compat/` on sys.path and `import nitorch_fastmath` resolves
 the hot-path modules (`sym`, `batched`, `qr`, `reduce`, `lie` -- expm and expm_derivatives --, `logm` -- logm and meanm, which
-the upstream package keeps in `lie` --, `simplex`, `special` and the helpers of `utils`) to the MI355X backend
+the upstream package keeps in `lie` --, `simplex`, `special`, `sugar` and the helpers of `utils`) to the MI355X backend
 `nitorch_fastmath_amd`.  Only the modules on the accelerated path exist here; the rest of
-the upstream package (realtransforms, stochastic, sugar) is out of
-scope of this backend."""
-from nitorch_fastmath_amd import sym, batched, qr, reduce, lie, logm, simplex, special, utils  # noqa: F401
+the upstream package (realtransforms, stochastic) is out of
+scope of this backend.  `sugar` is star-imported like upstream's `__init__` does (its `round` and `trace`
+become package attributes, as they are upstream)."""
+from nitorch_fastmath_amd import sym, batched, qr, reduce, lie, logm, simplex, special, sugar, utils  # noqa: F401
 from nitorch_fastmath_amd.sym import *       # noqa: F401,F403
 from nitorch_fastmath_amd.batched import *   # noqa: F401,F403
 from nitorch_fastmath_amd.qr import *        # noqa: F401,F403
 from nitorch_fastmath_amd.reduce import *    # noqa: F401,F403
+from nitorch_fastmath_amd.sugar import *     # noqa: F401,F403
 import sys as _sys
-for _m in ('sym', 'batched', 'qr', 'reduce', 'lie', 'logm', 'simplex', 'special', 'utils'):
+for _m in ('sym', 'batched', 'qr', 'reduce', 'lie', 'logm', 'simplex', 'special', 'sugar', 'utils'):
     _sys.modules[__name__ + '.' + _m] = globals()[_m]

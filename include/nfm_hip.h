@@ -431,6 +431,31 @@ int nfm_special_mvdigamma_backward(int dtype, int order, int64_t n, const void *
 int nfm_special_host_eval(int func, int dtype, int mode_or_order, double nu, int N, int K, int64_t n, const void *x,
                           const void *saved_out, const void *grad_out, void *result);
 
+/* ------------------------------------------------------------------ sugar ---- */
+
+/* X = A^-1 B for one N x N matrix and one N x K matrix of right-hand sides per batch element: `lmdiv`, and through
+ * swapped row / column strides `rmdiv` (X B = A  <=>  B^T X^T = A^T), `solvevec` (K = 1) and `inv` of the
+ * reference's `sugar.py:75-341`.  N, K in 1..NFM_SOLVE_MAX_DIM (NFM_ESIZE beyond, and for K above
+ * nfm_sugar_max_cols(dtype, N): solve B in blocks of columns).  Each operand is given as a raw pointer and the
+ * four strides of `struct nfm_operand` (elements; 0 = broadcast), and is read in place whatever they are.
+ * flags NFM_SOLVE_LU: Gaussian elimination with partial pivoting (getrf / getrs, what `torch.linalg.solve` runs);
+ * a singular record gives inf / NaN.  NFM_SOLVE_CHOL: A = L L^T from the LOWER triangle of A, the upper one is
+ * never read; a record with a pivot that is not positive gets NaN in every entry of its result (no exception).
+ * b == NULL: B is the identity and K must equal N (the inverse; NFM_SOLVE_LU then runs nfm_batch_inv).
+ * `out` may alias `b`.  Status precedence: NFM_EDTYPE; NFM_EINVAL negative count; NFM_ESIZE n_outer; NFM_ESIZE
+ * N or K; NFM_EINVAL unknown flag, or b == NULL with K != N; then a, b, out in this order: NFM_EINVAL for a null
+ * pointer with a non-empty batch, NFM_EALIGN.  An empty batch with null pointers succeeds without a launch. */
+#define NFM_SOLVE_LU 0
+#define NFM_SOLVE_CHOL 1
+#define NFM_SOLVE_MAX_DIM 8
+int nfm_sugar_solve(int dtype, int N, int K, int flags, int64_t n_outer, int64_t n_inner,
+                    const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                    const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                    void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream);
+/* largest K one nfm_sugar_solve call takes at order N (the register file bounds [A | B] per lane); NFM_EDTYPE /
+ * NFM_ESIZE for an unknown dtype / an order outside 1..NFM_SOLVE_MAX_DIM */
+int nfm_sugar_max_cols(int dtype, int N);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

@@ -1,7 +1,8 @@
 """nitorch_fastmath_amd -- MI355X-native (gfx950) backend for the per-element
 small-matrix hot path of nitorch-fastmath: `sym`, `batched`, `qr`, the NaN-omitting
 reductions of `reduce`, the matrix exponential of `lie`, the matrix logarithm / exponential barycentre
-of `logm`, the implicit-class softmax family of `simplex` and the Bessel / digamma functions of `special`,
+of `logm`, the implicit-class softmax family of `simplex`, the Bessel / digamma functions of `special` and the small solves of `sugar`
+(lmdiv / rmdiv / solvevec / inv),
 behind the reference's own Python function signatures.
 
 Host code is Python on PyTorch-ROCm (device memory, streams); the arithmetic is
@@ -9,7 +10,7 @@ hand-written HIP in `libnfm_hip.so`, reached through the C ABI of include/nfm_hi
 There is no CPU path: importing works anywhere, calling needs the built library and
 GPU tensors.
 """
-from . import sym, batched, reduce, qr, lie, logm, simplex, special, utils  # noqa: F401
+from . import sym, batched, reduce, qr, lie, logm, simplex, special, sugar, utils  # noqa: F401
 from .sym import *       # noqa: F401,F403
 from .batched import *   # noqa: F401,F403
 from .qr import *        # noqa: F401,F403

@@ -9,7 +9,7 @@ batchmatvec / batchinv / batchdet, eig_sym (eigenvalues, and eigenvectors throug
 as upstream's `_EigSym` `_impl/qr.py:684-735` intends), sum / nansum / mean / nanmean,
 max / min / nanmax / nanmin (the cotangent goes to the selected element), var / std / nanvar /
 nanstd, expm, logm, the simplex functions softmax / log_softmax / logsumexp (one saved tensor each) and the special
-functions besseli / besseli_ratio / mvdigamma.
+functions besseli / besseli_ratio / mvdigamma, lmdiv / rmdiv / solvevec.
 Everything else is forward-only and says so.
 """
 import torch
@@ -257,6 +257,32 @@ class BatchInvFn(torch.autograd.Function):
         (inv,) = ctx.saved_tensors
         it = inv.transpose(-1, -2)
         return -_small_matmul(_small_matmul(it, g), it), None
+
+
+class LmdivFn(torch.autograd.Function):
+    """X = A^-1 B (sugar.lmdiv on the kernel):  dB = A^-T G, the same kernel with a's row and column strides
+    swapped;  dA = -dB X^T.  `flag` SOLVE_CHOL is only reached with a constant (symmetric) A: dB = A^-1 G."""
+
+    @staticmethod
+    def forward(ctx, a, b, flag):
+        from . import sugar as S
+        with torch.no_grad():
+            x = S._solve(a, b, flag)
+        ctx.flag = flag
+        ctx.save_for_backward(a, x)
+        ctx.shapes = (a.shape, b.shape)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import sugar as S
+        a, x = ctx.saved_tensors
+        gb = S._solve(a if ctx.flag == _lib.SOLVE_CHOL else a.transpose(-1, -2), g, ctx.flag)
+        ga = None
+        if ctx.needs_input_grad[0]:
+            ga = _sum_to(-_small_matmul(gb, x.transpose(-1, -2)), ctx.shapes[0])
+        return ga, _sum_to(gb, ctx.shapes[1]) if ctx.needs_input_grad[1] else None, None
 
 
 class BatchDetFn(torch.autograd.Function):
