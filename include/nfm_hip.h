@@ -456,6 +456,39 @@ int nfm_sugar_solve(int dtype, int N, int K, int flags, int64_t n_outer, int64_t
  * NFM_ESIZE for an unknown dtype / an order outside 1..NFM_SOLVE_MAX_DIM */
 int nfm_sugar_max_cols(int dtype, int N);
 
+/* X = A^+ B for one M x N matrix and one M x K matrix of right-hand sides per batch element, by a one-sided Jacobi
+ * SVD held in the lane's registers: `lmdiv` / `rmdiv` / `solvevec` / `inv` of the reference's `sugar.py` with
+ * method 'svd' or 'pinv', and its non-square systems (least squares for M > N, minimum norm for M < N).  X is
+ * N x K.  M, N, K in 1..NFM_SVD_MAX_DIM (NFM_ESIZE beyond, and for K above nfm_svd_max_cols(dtype, M, N): solve B
+ * in blocks of columns).  The operand fields are those of nfm_sugar_solve; every layout is read in place.
+ * flags NFM_SVD_PLAIN ('svd'): X = V S^-1 U^T B with every singular value; a zero one gives inf / NaN for that
+ * record only.  NFM_SVD_PINV ('pinv'): the singular values sigma <= rcond sigma_max are dropped
+ * (`torch.linalg.pinv`'s reading of rcond); rcond is ignored under NFM_SVD_PLAIN.
+ * b == NULL: B is the M x M identity and K must equal M (the inverse / pseudo-inverse, N x M).  `out` may alias `b`
+ * when M == N.  The sweep loop of a record is bounded by NFM_SVD_MAX_SWEEPS whatever the input (NaN included).
+ * Status precedence: NFM_EDTYPE; NFM_EINVAL negative count; NFM_ESIZE n_outer; NFM_ESIZE M, N or K; NFM_EINVAL
+ * unknown flag, an rcond that is negative or NaN, or b == NULL with K != M; NFM_ESIZE K above the cap; then a, b,
+ * out in this order: NFM_EINVAL for a null pointer with a non-empty batch, NFM_EALIGN.  An empty batch with null
+ * pointers succeeds without a launch. */
+#define NFM_SVD_PLAIN 0
+#define NFM_SVD_PINV 1
+#define NFM_SVD_MAX_DIM 8
+#define NFM_SVD_MAX_SWEEPS 16
+int nfm_svd_solve(int dtype, int M, int N, int K, int flags, double rcond, int64_t n_outer, int64_t n_inner,
+                  const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                  const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                  void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream);
+/* the same arithmetic on the calling thread, for records in host memory (one after the other, through the routine
+ * the kernel runs): a check of the arithmetic that needs no device.  Same arguments and status codes; on success
+ * the return value is the largest number of sweeps a record took (0 for an empty batch and for M == 1). */
+int nfm_svd_solve_host(int dtype, int M, int N, int K, int flags, double rcond, int64_t n_outer, int64_t n_inner,
+                       const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                       const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                       void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc);
+/* largest K one nfm_svd_solve call takes for M x N records; NFM_EDTYPE / NFM_ESIZE for an unknown dtype / a size
+ * outside 1..NFM_SVD_MAX_DIM */
+int nfm_svd_max_cols(int dtype, int M, int N);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

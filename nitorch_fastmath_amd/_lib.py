@@ -25,6 +25,7 @@ SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
 SP_BESSELI, SP_BESSELI_BWD, SP_RATIO, SP_RATIO_BWD, SP_MVDIGAMMA, SP_MVDIGAMMA_BWD = range(6)
 SP_MAX_N = 8
 SOLVE_LU, SOLVE_CHOL, SOLVE_MAX_DIM = 0, 1, 8    # include/nfm_hip.h: NFM_SOLVE_*
+SVD_PLAIN, SVD_PINV, SVD_MAX_DIM, SVD_MAX_SWEEPS = 0, 1, 8, 16    # include/nfm_hip.h: NFM_SVD_*
 SIDE = {'left': 0, 'right': 1, 'both': 2}
 
 
@@ -70,6 +71,9 @@ SIGNATURES = {
     'nfm_special_host_eval': [_i, _i, _i, ctypes.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_sugar_solve': [_i, _i, _i, _i, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
     'nfm_sugar_max_cols': [_i, _i],
+    'nfm_svd_solve': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
+    'nfm_svd_solve_host': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64],
+    'nfm_svd_max_cols': [_i, _i, _i],
     'nfm_reduce_all': [_i, _i, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp],
     'nfm_reduce_dim_workspace_bytes': [_i, _i, _i64, _i64, _i64, _i],
     'nfm_reduce_dim': [_i, _i, _i, _i64, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],

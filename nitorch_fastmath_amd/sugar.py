@@ -1,17 +1,20 @@
 """
 "Syntactic sugar" linear algebra on MI355X -- drop-in for `nitorch_fastmath.sugar` (`sugar.py`).
 
-`lmdiv`, `rmdiv`, `solvevec` and `inv` on square matrices of order <= 8 run one lane-per-system HIP kernel
-(`nfm_sugar_solve`: Gaussian elimination with partial pivoting on `[A | B]`, or Cholesky from the lower
-triangle); the reference runs torch's batched LU, which is slow on tiny matrices.  Transposed, broadcast,
-padded and channel-first operands are read in place.  Larger and non-square systems and the `svd` / `pinv`
-methods take the reference's own torch composition on the device; the remaining names (`kron2`, `outer`,
-`trace`, `dot`, `mdot`, `is_orthonormal`, `round`) are torch compositions on the device, without a kernel.
+`lmdiv`, `rmdiv`, `solvevec` and `inv` on matrices of at most 8 rows and columns run one lane-per-system HIP
+kernel: `nfm_sugar_solve` for `lu` / `chol` on square matrices (Gaussian elimination with partial pivoting on
+`[A | B]`, or Cholesky from the lower triangle), `nfm_svd_solve` for `svd` / `pinv` and for every non-square
+system (one-sided Jacobi SVD on the rows of `[A | B]`: least squares for m > n, minimum norm for m < n).  The
+reference runs torch's batched LU / SVD, which are slow on tiny matrices.  Transposed, broadcast, padded and
+channel-first operands are read in place.  Orders above 8, and `svd` / `pinv` calls that need a gradient, take
+the reference's own torch composition on the device; the remaining names (`kron2`, `outer`, `trace`, `dot`,
+`mdot`, `is_orthonormal`, `round`) are torch compositions on the device, without a kernel.
 
-Deviations from the reference, on purpose (DESIGN.md, quirks Q33..Q36): `rmdiv` computes the documented
+Deviations from the reference, on purpose (DESIGN.md, quirks Q33..Q39): `rmdiv` computes the documented
 `A B^-1` for any `k`; `inv(method='chol')` returns the inverse for 2-D inputs too; on the kernel path a record
-that is not positive definite (`chol`) or is singular (`lu`) gets NaN / inf results instead of an exception
-for the whole batch; `kron2` keeps the reference's layout, which is not `torch.kron`'s.
+that is not positive definite (`chol`) or is singular (`lu`, `svd`) gets NaN / inf results instead of an
+exception for the whole batch; `kron2` keeps the reference's layout, which is not `torch.kron`'s; `pinv` drops
+the singular values `<= rcond sigma_max` from squared row norms; `inv(method='svd', out=)` fills `out`.
 """
 __all__ = [
     'kron2',
@@ -33,7 +36,10 @@ from ._dispatch import Batch, broadcast_shapes, call, dtype_code, expand_batch, 
 
 MAX_ORDER = _lib.SOLVE_MAX_DIM
 _FLAGS = {'lu': _lib.SOLVE_LU, 'chol': _lib.SOLVE_CHOL}
+_SVD_FLAGS = {'svd': _lib.SVD_PLAIN, 'pinv': _lib.SVD_PINV}
+SVD_MAX_DIM = _lib.SVD_MAX_DIM
 _caps = {}
+_svd_caps = {}
 
 
 def max_cols(dtype, n):
@@ -42,6 +48,14 @@ def max_cols(dtype, n):
     if key not in _caps:
         _caps[key] = int(_lib.lib().nfm_sugar_max_cols(dtype_code(dtype), n))
     return _caps[key]
+
+
+def svd_max_cols(dtype, m, n):
+    """Columns of `b` one launch takes for an `m x n` system (the library's table, `nfm_svd_max_cols`)."""
+    key = (dtype, m, n)
+    if key not in _svd_caps:
+        _svd_caps[key] = int(_lib.lib().nfm_svd_max_cols(dtype_code(dtype), m, n))
+    return _svd_caps[key]
 
 
 def _method(method, a):
@@ -67,6 +81,18 @@ def _launch(dev, dtype, n, k, flag, a, b, out):
     o = bt.operands
     fb = (None, 0, 0, 0, 0) if b is None else _fields(o[1])
     call(_lib.lib().nfm_sugar_solve, dev, dtype_code(dtype), n, k, flag, bt.n_outer, bt.n_inner,
+         *_fields(o[0]), *fb, *_fields(o[-1]))
+    bt.finish()
+
+
+def _svd_launch(dev, dtype, m, n, k, flag, rcond, a, b, out):
+    """one nfm_svd_solve call; a / b / out share their batch dims (views); b None: the identity"""
+    batch = out.shape[:-2]
+    tensors = [a, out] if b is None else [a, b, out]
+    bt = Batch(batch, tensors, [2] * len(tensors))
+    o = bt.operands
+    fb = (None, 0, 0, 0, 0) if b is None else _fields(o[1])
+    call(_lib.lib().nfm_svd_solve, dev, dtype_code(dtype), m, n, k, flag, float(rcond), bt.n_outer, bt.n_inner,
          *_fields(o[0]), *fb, *_fields(o[-1]))
     bt.finish()
 
@@ -110,6 +136,39 @@ def _solve(a, b, flag, out=None):
     return out
 
 
+def _svd_ok(a):
+    return 0 < a.shape[-1] <= SVD_MAX_DIM and 0 < a.shape[-2] <= SVD_MAX_DIM
+
+
+def _svd_solve(a, b, flag, rcond, out=None):
+    """X = a^+ b on the kernel: a (..., m, n), m, n <= 8; b (..., m, k) or None (identity, k = m); forward only.
+    Column blocks as in `_solve`."""
+    dev, dtype = a.device, a.dtype
+    m, n = a.shape[-2:]
+    k = m if b is None else b.shape[-1]
+    batch = a.shape[:-2] if b is None else broadcast_shapes(a.shape[:-2], b.shape[:-2])
+    shape = tuple(batch) + (n, k)
+    if out is None:
+        out = _like(b, shape, dtype, dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev:
+        raise ValueError(f'out= must be a {dtype} tensor of shape {shape} on {dev}')
+    if out.numel() == 0:
+        return out
+    a = expand_batch(batch, a, 2)
+    if b is None:
+        _svd_launch(dev, dtype, m, n, m, flag, rcond, a, None, out)
+        return out
+    b = expand_batch(batch, b, 2)
+    cap = svd_max_cols(dtype, m, n)
+    for c0 in range(0, k, cap):
+        c1 = min(c0 + cap, k)
+        if c0 == 0 and c1 == k:
+            _svd_launch(dev, dtype, m, n, k, flag, rcond, a, b, out)
+        else:
+            _svd_launch(dev, dtype, m, n, c1 - c0, flag, rcond, a, b[..., c0:c1], out[..., c0:c1])
+    return out
+
+
 def _check_out(out, *tensors):
     if out is not None and torch.is_grad_enabled() and any(t.requires_grad for t in tensors + (out,)):
         raise RuntimeError('out= is not supported for tensors that require grad')
@@ -144,13 +203,19 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
 
     a : `(..., m, n)`, b : `(..., m, k)` -> `(..., n, k)`; batch dims broadcast.
     method : `{'lu', 'chol', 'svd', 'pinv'}`; non-square `a` always takes `pinv`.
-    Square `a` of order <= 8 with `lu` or `chol` runs the HIP kernel; `chol` reads the lower triangle only."""
+    `a` with m, n <= 8 runs a HIP kernel: elimination (`lu`), Cholesky from the lower triangle only (`chol`), or
+    the Jacobi SVD (`svd`, `pinv`, every non-square `a`; forward only -- with a gradient: the torch composition).
+    `pinv` drops the singular values `<= rcond sigma_max`; `svd` divides by every one of them."""
     dev, dtype, (a, b) = prepare(None, a, b, grad_ok=True)
     _check_out(out, a, b)
     method = _method(method, a)
     if b.shape[-2] != a.shape[-2]:
         raise ValueError(f'system {tuple(a.shape[-2:])} and right-hand side {tuple(b.shape[-2:])} do not match')
-    if method not in _FLAGS or a.shape[-1] > MAX_ORDER or a.shape[-1] == 0:
+    if method in _SVD_FLAGS:
+        if not _svd_ok(a) or needs_grad(a, b):
+            return _torch_lmdiv(a, b, method, rcond, out)
+        return _svd_solve(a, b, _SVD_FLAGS[method], rcond, out)
+    if a.shape[-1] > MAX_ORDER or a.shape[-1] == 0:
         return _torch_lmdiv(a, b, method, rcond, out)
     if needs_grad(a, b):
         if method == 'chol' and a.requires_grad:     # differentiates through the lower triangle only, like torch
@@ -174,7 +239,8 @@ def rmdiv(a, b, method='lu', rcond=1e-15, out=None):
 
 def inv(a, method='lu', rcond=1e-15, out=None):
     """Matrix inversion (sugar.py:194-258).  `lu`: `batchinv` up to order 16; `chol`: the kernel of `lmdiv`
-    against an identity generated in registers (order <= 8), for every batch rank."""
+    against an identity generated in registers (order <= 8), for every batch rank; `svd` / `pinv` and every
+    non-square `a` (m, n <= 8): the Jacobi SVD kernel against the identity, `(..., n, m)`."""
     dev, dtype, (a,) = prepare(None, a, grad_ok=True)
     _check_out(out, a)
     method = _method(method, a)
@@ -195,6 +261,8 @@ def inv(a, method='lu', rcond=1e-15, out=None):
             return _solve(a, None, _lib.SOLVE_CHOL, out)
         eye = torch.eye(n, dtype=dtype, device=dev)
         return torch.cholesky_solve(eye, torch.linalg.cholesky(a, upper=False), upper=False, out=out)
+    if _svd_ok(a) and not needs_grad(a):
+        return _svd_solve(a, None, _SVD_FLAGS[method], rcond, out)
     if method == 'svd':
         u, s, v = torch.svd(a)
         return give(v.matmul(u.transpose(-1, -2) / s[..., None]))
