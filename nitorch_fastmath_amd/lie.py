@@ -96,7 +96,9 @@ def expm(X, basis=None, max_order=10000, tol=1e-32):
 
     X : `(..., D, D)` log-matrix, or `(..., F)` parameters when `basis` `(..., F, D, D)` is given.
     max_order, tol : the series stops at the degree whose term bound passes the reference's test
-        `sum(T_n^2) <= D^2 tol` (at most `max_order`), after scaling by 2^-s.
+        `sum(T_n^2) <= D^2 tol` (at most `max_order`), after scaling by 2^-s.  The derivative
+        kernels (the backward here, dX / dB / hX of `expm_derivatives`) run one (L) or two (L2) degrees further,
+        still at most `max_order`: their terms lag the exponential's by that many powers of the matrix.
     Returns `(..., D, D)`.  Differentiable: the backward runs the Frechet kernel, L(M^T, G).
     """
     from ._autograd import ExpmFn

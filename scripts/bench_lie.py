@@ -88,6 +88,7 @@ def main():
         p = (torch.randn(n, F, device='cuda', generator=gen, dtype=torch.float64) * 0.3).to(dtype)
         M = torch.einsum('nf,fij->nij', p, B).unsqueeze(-3)
         m, s = degree_and_squarings(M[:2000, 0].cpu())
+        m = m + 1                                # the L kernel runs one degree past the exponential's
         el = p.element_size()
         fl = F * (3 * 2 * D ** 3 * m + 6 * D ** 3 * s)
         bl = (D * D + F * D * D) * el

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Accuracy table of lie.expm / expm_derivatives against the 40-digit truth of tests/golden/lie.npz:
 per (dtype, D) the worst error max|K - T| / max|T| of the kernel and of the reference, and the worst ratio
-err / (D eps (1 + ||X||_1)) -- the constant C of the test bound C D eps (1 + ||X||_1).
+err / (D eps (1 + ||X||_1)) -- the constant C of the test bound C D eps (1 + ||X||_1).  The Frechet kernels get the
+same per input class of tests/_lie_ref.py: float32 at D = 1..4 and both depths, float64 on tests/golden/lie_frechet.npz.
 
     python scripts/lie_accuracy.py [--md out.md]"""
 import argparse
@@ -18,7 +19,7 @@ import nitorch_fastmath_amd as N  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--md')
-    a = ap.parse_args()
+    args = ap.parse_args()
     g = np.load(os.path.join(ROOT, 'tests', 'golden', 'lie.npz'))
     lines = ['| dtype | D | kernel worst err | reference worst err | kernel worst C | reference worst C (finite) |',
              '|---|---|---|---|---|---|']
@@ -48,6 +49,36 @@ def main():
         c = max((e1 / b).max(), (e2 / b).max())
         worst_d = max(worst_d, c)
         dl.append(f'| | {D} | {e1.max():.2e} | {e2.max():.2e} | {c:.2f} |')
+    # Frechet kernels by input class (tests/_lie_ref.py): 2000 records per class, float32 against the float64 block
+    # identities with the float32 identities as reference; float64 on the 96-record 40-digit fixture
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import _lie_ref as R
+    from nitorch_fastmath_amd import lie
+    fl = ['', '| Frechet kernels | D | depth | class | kernel worst err | kernel worst C | reference worst err | '
+          'reference worst C |', '|---|---|---|---|---|---|---|---|']
+
+    def rows(dn, D, depth, x, a, b, truth, ref, where):
+        dtype = R.DT[dn]
+        bb = b if depth == 2 else None
+        k = lie._frechet(x.cuda(), a.cuda(), None if bb is None else bb.cuda(), 10000, 1e-32).cpu()
+        t = truth(bb)
+        r = ref(bb)
+        for cls, sl in where:
+            ek, er = R.err(k[sl], t[sl]), R.err(r[sl], t[sl])
+            u = R.unit(x[sl], dtype)
+            fl.append(f'| {dn} | {D} | {depth} | {R.cname(cls)} | {float(ek.max()):.2e} | {float((ek / u).max()):.2f} | '
+                      f'{float(er.max()):.2e} | {float((er / u).max()):.2f} |')
+
+    for D in (1, 2, 3, 4):
+        x, a, b, where = R.all_inputs(2000, D, 'f32')
+        for depth in (1, 2):
+            rows('f32', D, depth, x, a, b, lambda bb: R.frechet_truth64(x, a, bb),
+                 lambda bb: R.frechet_ref(x, a, bb, torch.float32), where)
+    for D in R.FIXTURE_ORDERS:
+        x, a, b, L, L2 = R.fixture_records(D)
+        for depth in (1, 2):
+            rows('f64', D, depth, x, a, b, lambda bb: L if bb is None else L2,
+                 lambda bb: R.frechet_truth64(x, a, bb), R.fixture_classes())
     # 10^6 random matrices (randn * 0.7) against matrix_exp in float64 on the device, as tests/test_gpu_lie.py::test_scale
     sl = ['', '| 10^6 x randn * 0.7 vs matrix_exp (float64) | D | worst err | worst C |', '|---|---|---|---|']
     gen = torch.Generator(device='cuda').manual_seed(7)
@@ -58,10 +89,10 @@ def main():
             err = (N.lie.expm(x).double() - t).abs().amax((-2, -1)) / t.abs().amax((-2, -1))
             c = err / (D * torch.finfo(dtype).eps * (1 + x.double().abs().sum(-2).amax(-1)))
             sl.append(f'| {str(dtype)[6:]} | {D} | {float(err.max()):.2e} | {float(c.max()):.2f} |')
-    out = '\n'.join(lines + dl + sl + ['', f'worst C on the fixture: expm {worst:.2f}, derivatives {worst_d:.2f}']) + '\n'
+    out = '\n'.join(lines + dl + fl + sl + ['', f'worst C on the fixture: expm {worst:.2f}, derivatives {worst_d:.2f}']) + '\n'
     print(out)
-    if a.md:
-        open(a.md, 'w').write(out)
+    if args.md:
+        open(args.md, 'w').write(out)
 
 
 if __name__ == '__main__':

@@ -129,3 +129,117 @@ def test_lie_kernels_in_the_census():
     assert not any('ExpmFrechetOp<float, 5' in n for n in fr)
     f4 = [names[n] for n in exp if 'ExpmOp<float, 4>' in n]
     assert f4 and max(k['vgpr'] for k in f4) <= 256
+
+
+# ------------------------------------------------------------------------------------------ Frechet derivatives:
+# the fixture, the float64 truth and the model of tests/_lie_ref.py, before a GPU sees their bounds
+def test_frechet_fixture_shapes_and_classes():
+    import _lie_ref as R
+    g = R.fixture()
+    per_order = sum(R.FIXTURE_COUNT[c[0]] for c in R.CLASSES)
+    assert per_order == 96 and R.fixture_classes()[-1][1].stop == 96
+    for D in R.FIXTURE_ORDERS:
+        for k in ('x', 'a', 'b', 'L', 'L2'):
+            assert g[f'{k}_{D}'].shape == (96, D, D) and g[f'{k}_{D}'].dtype == np.float64
+            assert np.isfinite(g[f'{k}_{D}']).all()
+        x = g[f'x_{D}']
+        n1 = np.abs(x).sum(1).max(1)
+        for cls, sl in R.fixture_classes():
+            assert np.allclose(n1[sl], cls[1], rtol=1e-12), (D, cls)
+            if cls[0] == 'skew':
+                assert np.array_equal(x[sl], -x[sl].transpose(0, 2, 1))
+            if cls[0] == 'nilp':
+                assert not np.tril(x[sl]).any()
+
+
+def test_frechet_truth64_agrees_with_the_40_digit_fixture():
+    """licenses the float64 block identities as the truth of float32 results: 1e-13 (1 + ||X||_1) relative"""
+    import _lie_ref as R
+    for D in R.FIXTURE_ORDERS:
+        x, a, b, L, L2 = R.fixture_records(D)
+        for T, bb in ((L, None), (L2, b)):
+            e = R.err(R.frechet_truth64(x, a, bb), T) / (1 + R.norm1(x))
+            assert float(e.max()) <= 1e-13, (D, bb is None, float(e.max()))
+            assert R.fixture_c_ref(D, 1 if bb is None else 2)
+    # the series of a nilpotent matrix ends: the finite sum is the same truth
+    x, a, b, L, L2 = R.fixture_records(4)
+    sl = slice(78, 96)
+    assert float(R.err(R.series_frechet(x[sl], a[sl]), L[sl]).max()) <= 1e-14
+    assert float(R.err(R.series_frechet(x[sl], a[sl], b[sl]), L2[sl]).max()) <= 1e-14
+
+
+N_ACC = 2000           # the draw of test_gpu_lie_derivatives.py (3a)
+N_MODEL = 500          # the first records of every class of that same draw: X, A and B are the GPU tests' own
+
+
+@pytest.mark.parametrize('depth', [1, 2])
+@pytest.mark.parametrize('D', [1, 2, 3, 4])
+def test_frechet_model_meets_the_float32_bounds(D, depth):
+    """the bars of test_gpu_lie_derivatives.py (3a) are attainable by the kernel's formulas in float32"""
+    import _lie_ref as R
+    x, a, b, where = R.all_inputs(N_ACC, D, 'f32', first=N_MODEL)
+    b = b if depth == 2 else None
+    R.class_verdicts(R.frechet_model(x, a, b, torch.float32), R.frechet_truth64(x, a, b),
+                     R.frechet_ref(x, a, b, torch.float32), x, torch.float32, where, f'model float32 D={D} L{depth}')
+
+
+@pytest.mark.parametrize('depth', [1, 2])
+@pytest.mark.parametrize('D', [2, 3, 4])
+def test_frechet_model_meets_the_float64_bounds(D, depth):
+    import _lie_ref as R
+    x, a, b, L, L2 = R.fixture_records(D)
+    bb = b if depth == 2 else None
+    R.class_verdicts(R.frechet_model(x, a, bb, torch.float64), L2 if depth == 2 else L, R.frechet_truth64(x, a, bb),
+                     x, torch.float64, R.fixture_classes(), f'model float64 fixture D={D} L{depth}')
+    x, a, b, where = R.all_inputs(N_ACC, D, 'f64', first=N_MODEL)
+    bb = b if depth == 2 else None
+    c = R.c_of(R.frechet_model(x, a, bb, torch.float64), R.frechet_truth64(x, a, bb), x, torch.float64)
+    for cls, sl in where:
+        msg = R.verdict(c[sl], 2 * R.c_bound(R.fixture_c_ref(D, depth)[cls], D), f'model float64 D={D} L{depth} {cls}')
+        assert msg is None, msg
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+@pytest.mark.parametrize('D', [1, 2, 3, 4])
+def test_frechet_model_closed_forms_and_truncation(dn, D):
+    """3b and 3f on the model: X = 0, X = c I, a nilpotent X, and a truncated series in the dtype against the same
+    series in float64"""
+    import _lie_ref as R
+    dtype = R.DT[dn]
+    x, a, b = R.inputs(('gen', 2.0), 300, D, dn)
+    ad, bd = a.double(), b.double()
+    sym = (ad @ bd + bd @ ad) / 2
+    z = torch.zeros_like(x)
+    assert torch.equal(R.frechet_model(z, a, None, dtype), a)
+    R.held(R.frechet_model(z, a, b, dtype), sym, z, dtype, R.C_FLOOR, 'model L2 at X = 0')
+    for c in (-3.0, 0.5, 6.0):
+        xi = (c * torch.eye(D, dtype=dtype)).expand(300, D, D)
+        ec = float(np.exp(c))
+        R.held(R.frechet_model(xi, a, None, dtype), ec * ad, xi, dtype, R.C_FLOOR, f'model L at {c} I')
+        R.held(R.frechet_model(xi, a, b, dtype), ec * sym, xi, dtype, R.C_FLOOR, f'model L2 at {c} I')
+        R.held(R.frechet_truth64(xi, a, b), ec * sym, xi, torch.float64, R.C_FLOOR, f'identity L2 at {c} I')
+    # A = X, and L2 symmetric in its directions (each order against the truth, and against each other)
+    ex = torch.linalg.matrix_exp(x.double())
+    k = R.frechet_model(x, x, None, dtype)
+    R.held(k, x.double() @ ex, x, dtype, R.C_FLOOR, 'model L(X, X) = X expm(X)')
+    R.held(k, ex @ x.double(), x, dtype, R.C_FLOOR, 'model L(X, X) = expm(X) X')
+    t2 = R.frechet_truth64(x, a, b) if D > 1 else torch.exp(x.double()) * ad * bd
+    kab, kba = R.frechet_model(x, a, b, dtype), R.frechet_model(x, b, a, dtype)
+    c2 = R.C_FLOOR if dn == 'f32' else 2 * R.C_FLOOR          # float64: the truth is of the same precision
+    R.held(kab, t2, x, dtype, c2, 'model L2(X, A, B)')
+    R.held(kba, t2, x, dtype, c2, 'model L2(X, B, A)')
+    R.held(kab, kba.double(), x, dtype, 2 * c2, 'model L2 symmetric')
+    for e in (-20, 7):
+        assert torch.equal(R.frechet_model(x, a * 2.0 ** e, None, dtype), R.frechet_model(x, a, None, dtype) * 2.0 ** e)
+    if D == 1:
+        return                       # no nilpotent scalar; order 1 is a closed form that ignores max_order / tol
+    xn, an, bn = R.inputs(('nilp', 5.0), 300, D, dn)
+    R.held(R.frechet_model(xn, an, bn, dtype), R.series_frechet(xn, an, bn), xn, dtype, R.C_FLOOR, 'model nilpotent')
+    for max_order, tol in ((1, 1e-32), (2, 1e-32), (5, 1e-32), (10000, 1e-4), (10000, 1e-12)):
+        for cls in (('gen', 0.5), ('gen', 8.0)):
+            xc, ac, bc = R.inputs(cls, 300, D, dn)
+            for bb in (None, bc):
+                k = R.frechet_model(xc, ac, bb, dtype, max_order, tol)
+                c = R.truncated_verdict(k, xc, ac, bb, dtype, max_order, tol)
+                msg = R.verdict(c, R.C_FLOOR, f'model {dn} D={D} {cls} max_order={max_order} tol={tol:g}')
+                assert msg is None, msg
