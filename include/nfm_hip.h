@@ -489,6 +489,42 @@ int nfm_svd_solve_host(int dtype, int M, int N, int K, int flags, double rcond, 
  * outside 1..NFM_SVD_MAX_DIM */
 int nfm_svd_max_cols(int dtype, int M, int N);
 
+/* --------------------------------------------------------- realtransforms ---- */
+
+/* Discrete cosine / sine transforms of types I, II, III along the middle axis of a contiguous (outer, N, inner)
+ * view (`realtransforms.py`: dct, dst and, with norm and type flipped by the caller, idct, idst), one line per
+ * lane as a direct sum against a table of cosines / sines that each workgroup builds for itself: one read and
+ * one write per element, no workspace, no state.  With the unnormalised ("backward") matrices
+ *     DCT-II  2 cos(pi k (2n+1) / 2N)                          DST-II  2 sin(pi (k+1) (2n+1) / 2N)
+ *     DCT-III x0 + 2 sum_{n>=1} x_n cos(pi (2k+1) n / 2N)      DST-III (-1)^k x_{N-1} + 2 sum_{n<N-1} x_n sin(pi (2k+1) (n+1) / 2N)
+ *     DCT-I   x0 + (-1)^k x_{N-1} + 2 sum x_n cos(pi k n / (N-1))   DST-I  2 sin(pi (k+1) (n+1) / (N+1))
+ * norm NFM_RT_FORWARD scales by 1 / 2L (L = N; N - 1 for DCT-I, N + 1 for DST-I), NFM_RT_ORTHO by 1 / sqrt(2L) and
+ * rescales the end terms so that the matrix is orthogonal (scipy's `orthogonalize=True`), NFM_RT_ORTHO_SCIPY is the
+ * reference's 'ortho_scipy': 'ortho' for every DCT and for type I; for DST-II the FIRST output and for DST-III the
+ * FIRST input carry the sqrt(2) correction instead of the last.  All of it happens in the one launch.
+ * transpose != 0 applies the transposed matrix (the adjoint: what a backward pass needs).  `out` may alias `x`.
+ * N in 1..nfm_rt_max_len(dtype); DCT-I needs N >= 2.
+ * Status precedence: NFM_EDTYPE; NFM_EINVAL negative N / outer / inner; NFM_EINVAL unknown kind, type, norm or
+ * transpose, N == 0, DCT-I with N == 1; NFM_ESIZE an element count past int64; NFM_RT_EFALLBACK N above the cap (the
+ * caller's own route: the Python facade composes the transform from torch.fft there); then x, out: NFM_EINVAL
+ * for a null pointer with a non-empty batch, NFM_EALIGN.  An empty batch succeeds without a launch. */
+#define NFM_RT_DCT 0
+#define NFM_RT_DST 1
+#define NFM_RT_BACKWARD 0
+#define NFM_RT_FORWARD 1
+#define NFM_RT_ORTHO 2
+#define NFM_RT_ORTHO_SCIPY 3
+#define NFM_RT_MAX_N 256          /* no build serves longer lines; nfm_rt_max_len is the cap of this build */
+#define NFM_RT_EFALLBACK (-100)   /* the line is longer than the kernels serve */
+int nfm_rt_transform(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer, int64_t inner,
+                     const void *x, void *out, void *stream);
+/* the same per-line routine on the calling thread, for tensors in host memory: a check of the arithmetic that
+ * needs no device.  Same arguments and status codes; N up to NFM_RT_MAX_N whatever the kernels' cap. */
+int nfm_rt_transform_host(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer,
+                          int64_t inner, const void *x, void *out);
+/* longest line nfm_rt_transform takes for the dtype (NFM_EDTYPE for an unknown one) */
+int nfm_rt_max_len(int dtype);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

@@ -743,3 +743,19 @@ class MvDigammaFn(torch.autograd.Function):
         from . import special
         (x,) = ctx.saved_tensors
         return special._digamma_backward(x, g, ctx.order), None
+
+
+class RealTransformFn(torch.autograd.Function):
+    """realtransforms: DCT / DST along `dims`; the backward pass is the transposed matrix along the same axes,
+    issued through this Function (linear operator: any order of derivative)."""
+
+    @staticmethod
+    def forward(ctx, x, kind, type, norm, dims, transpose):
+        from . import realtransforms
+        ctx.args = (kind, type, norm, dims, transpose)
+        return realtransforms._apply(x.detach(), list(dims), kind, type, norm, transpose)
+
+    @staticmethod
+    def backward(ctx, g):
+        kind, type, norm, dims, transpose = ctx.args
+        return RealTransformFn.apply(g, kind, type, norm, dims, not transpose), None, None, None, None, None

@@ -227,6 +227,7 @@ const char *nfm_strerror(int code)
     case NFM_ESIZE: return "matrix order outside 1..16 or batch too large";
     case NFM_EALIGN: return "pointer not aligned to the element size";
     case NFM_EWORKSPACE: return "workspace too small";
+    case NFM_RT_EFALLBACK: return "line longer than the transform kernels serve";
     default: return code > 0 ? hipGetErrorString(static_cast<hipError_t>(code)) : "unknown error";
     }
 }
