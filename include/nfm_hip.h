@@ -524,6 +524,15 @@ int nfm_rt_transform_host(int dtype, int kind, int type, int norm, int transpose
                           int64_t inner, const void *x, void *out);
 /* longest line nfm_rt_transform takes for the dtype (NFM_EDTYPE for an unknown one) */
 int nfm_rt_max_len(int dtype);
+/* The same transform as a matrix product on the matrix cores, for the long axes the lane kernels leave out: a
+ * workgroup stages 32 whole lines in LDS and contracts them against the same table with v_mfma_*_16x16x4 (exact
+ * float32 / float64 fma chains).  Same arguments, checks and status codes as nfm_rt_transform; every N in
+ * 1..NFM_RT_MAX_N is served (NFM_RT_EFALLBACK above), `out` may alias `x`, no workspace, no host sync. */
+int nfm_rt_transform_mm(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer,
+                        int64_t inner, const void *x, void *out, void *stream);
+/* longest line a caller should route to nfm_rt_transform_mm for the dtype: the largest of 128 / 256 at which it
+ * is not slower than the torch.fft composition in both layouts, 64 if neither (NFM_EDTYPE for an unknown dtype) */
+int nfm_rt_mm_max_len(int dtype);
 
 /* ------------------------------------------------------------------- misc ---- */
 

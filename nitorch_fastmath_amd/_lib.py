@@ -80,6 +80,8 @@ SIGNATURES = {
     'nfm_rt_transform': [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp],
     'nfm_rt_transform_host': [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp],
     'nfm_rt_max_len': [_i],
+    'nfm_rt_transform_mm': [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp],
+    'nfm_rt_mm_max_len': [_i],
     'nfm_reduce_all': [_i, _i, _i, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp],
     'nfm_reduce_dim_workspace_bytes': [_i, _i, _i64, _i64, _i64, _i],
     'nfm_reduce_dim': [_i, _i, _i, _i64, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],

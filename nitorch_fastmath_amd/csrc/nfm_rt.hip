@@ -8,7 +8,7 @@
 //               the outputs through a second image.
 // Each workgroup builds the table of 2 cos / 2 sin(pi m / D) in LDS in its prologue; the transform reads it at
 // wave-uniform addresses.  N is a kernel argument: six kernels in all.  The arithmetic is in nfm_rt_ops.hpp.
-#include "nfm_rt_ops.hpp"
+#include "nfm_rt_mm.hpp"
 #include "nfm_simplex_ops.hpp" // tile_in / tile_out
 
 namespace nfm {
@@ -27,14 +27,16 @@ using simplex::tile_out;
 static_assert(NFM_RT_MAX_LEN_F32 >= 1 && NFM_RT_MAX_LEN_F32 <= NFM_RT_MAX_N, "float32 cap");
 static_assert(NFM_RT_MAX_LEN_F64 >= 1 && NFM_RT_MAX_LEN_F64 <= NFM_RT_MAX_N, "float64 cap");
 
-constexpr size_t kLdsPlain = 64 * 1024, kLdsOptIn = 160 * 1024;
-
-struct Args {
-    Plan p;
-    int64_t outer, inner;
-    const void *x;
-    void *o;
-};
+// lengths the facade routes to the matrix-instruction kernel (nfm_rt_mm_max_len): per dtype the largest of
+// {128, 256} at which it is not slower than the torch.fft composition in both layouts, 64 (route off) if neither
+#ifndef NFM_RT_MM_MAX_LEN_F32
+#define NFM_RT_MM_MAX_LEN_F32 256
+#endif
+#ifndef NFM_RT_MM_MAX_LEN_F64
+#define NFM_RT_MM_MAX_LEN_F64 256
+#endif
+constexpr bool mm_cap_ok(int n) { return n == 64 || n == 128 || n == 256; }
+static_assert(mm_cap_ok(NFM_RT_MM_MAX_LEN_F32) && mm_cap_ok(NFM_RT_MM_MAX_LEN_F64), "routing cap: 64, 128 or 256");
 
 template <typename T, int VEC>
 struct Pack {
@@ -82,8 +84,6 @@ struct GlobalOut {
         }
     }
 };
-
-constexpr int table_len(int P) { return (P + 3) & ~3; } // keeps what follows 16-byte aligned
 
 template <typename T, int VEC, bool LAST>
 __global__ __launch_bounds__(256) void rt_kernel(const Args a)
@@ -225,8 +225,10 @@ static int run_host(const Args &a)
 
 static int max_len(int dtype) { return dtype == NFM_F64 ? NFM_RT_MAX_LEN_F64 : NFM_RT_MAX_LEN_F32; }
 
+enum Path { kLane, kHost, kMm }; // who runs the checked call; only the lane kernels have a cap below NFM_RT_MAX_N
+
 static int entry(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer, int64_t inner,
-                 const void *x, void *out, int host, void *stream)
+                 const void *x, void *out, Path path, void *stream)
 {
     if (dtype != NFM_F32 && dtype != NFM_F64) return NFM_EDTYPE;
     if (N < 0 || outer < 0 || inner < 0) return NFM_EINVAL;
@@ -236,7 +238,7 @@ static int entry(int dtype, int kind, int type, int norm, int transpose, int64_t
     if (transpose != 0 && transpose != 1) return NFM_EINVAL;
     if (N < 1 || (N == 1 && kind == NFM_RT_DCT && type == 1)) return NFM_EINVAL;
     if (outer > 0 && inner > 0 && (outer > INT64_MAX / inner || outer * inner > INT64_MAX / N)) return NFM_ESIZE;
-    if (N > (host ? NFM_RT_MAX_N : max_len(dtype))) return NFM_RT_EFALLBACK;
+    if (N > (path == kLane ? max_len(dtype) : NFM_RT_MAX_N)) return NFM_RT_EFALLBACK;
     const bool nonempty = outer > 0 && inner > 0;
     const size_t elem = dtype == NFM_F32 ? 4 : 8;
     for (const void *ptr : {x, static_cast<const void *>(out)}) {
@@ -248,7 +250,8 @@ static int entry(int dtype, int kind, int type, int norm, int transpose, int64_t
     a.p = make_plan(kind, type, norm, transpose, (int)N);
     a.outer = outer, a.inner = inner;
     a.x = x, a.o = out;
-    if (host) return by_dtype(dtype, [&](auto t) { return run_host<decltype(t)>(a); });
+    if (path == kHost) return by_dtype(dtype, [&](auto t) { return run_host<decltype(t)>(a); });
+    if (path == kMm) return dispatch_mm(dtype, a, stream);
     return by_dtype(dtype, [&](auto t) { return dispatch<decltype(t)>(a, stream); });
 }
 
@@ -268,13 +271,25 @@ int nfm_rt_max_len(int dtype)
 int nfm_rt_transform(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer, int64_t inner,
                      const void *x, void *out, void *stream)
 {
-    return rt::entry(dtype, kind, type, norm, transpose, N, outer, inner, x, out, 0, stream);
+    return rt::entry(dtype, kind, type, norm, transpose, N, outer, inner, x, out, rt::kLane, stream);
 }
 
 int nfm_rt_transform_host(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer,
                           int64_t inner, const void *x, void *out)
 {
-    return rt::entry(dtype, kind, type, norm, transpose, N, outer, inner, x, out, 1, nullptr);
+    return rt::entry(dtype, kind, type, norm, transpose, N, outer, inner, x, out, rt::kHost, nullptr);
+}
+
+int nfm_rt_mm_max_len(int dtype)
+{
+    if (dtype != NFM_F32 && dtype != NFM_F64) return NFM_EDTYPE;
+    return dtype == NFM_F64 ? NFM_RT_MM_MAX_LEN_F64 : NFM_RT_MM_MAX_LEN_F32;
+}
+
+int nfm_rt_transform_mm(int dtype, int kind, int type, int norm, int transpose, int64_t N, int64_t outer,
+                        int64_t inner, const void *x, void *out, void *stream)
+{
+    return rt::entry(dtype, kind, type, norm, transpose, N, outer, inner, x, out, rt::kMm, stream);
 }
 
 } // extern "C"

@@ -3,14 +3,17 @@ Discrete cosine and sine transforms on MI355X -- drop-in for `nitorch_fastmath.r
 (`realtransforms.py`): `dct`, `dst`, `idct`, `idst` along one axis and `dctn`, `dstn`, `idctn`, `idstn` along
 several, types 1, 2 and 3, norms 'backward', 'forward', 'ortho' and the reference's 'ortho_scipy'.
 
-A transform along an axis of length N is a fixed N x N matrix applied to every line.  One lane owns one line
-(`nfm_rt.hip`): the line is read once, every output is a direct sum against a table of cosines / sines that the
-workgroup builds for itself, and the normalisation (global factor, end-term corrections) happens in the same
-launch.  Any `dim` of a contiguous tensor (or of a dim-permuted view of one) runs in place of a copy; other
+A transform along an axis of length N is a fixed N x N matrix applied to every line.  Up to `max_len(dtype)` one
+lane owns one line (`nfm_rt.hip`): the line is read once, every output is a direct sum against a table of
+cosines / sines that the workgroup builds for itself, and the normalisation (global factor, end-term
+corrections) happens in the same launch.  From there up to `mm_max_len(dtype)` (256 at most: the axes of whole
+volumes) a workgroup owns 32 lines and forms the same sums as a matrix product on the matrix cores
+(`nfm_rt_mm.hip`): the same table, the same fma chain per output, one read and one write per element, no
+workspace.  Any `dim` of a contiguous tensor (or of a dim-permuted view of one) runs in place of a copy; other
 non-contiguous inputs take one `contiguous()`.  The n-d forms are one launch per axis, the first from the input
-into the result, the rest in place on the result.  float32 and float64 GPU tensors with axes up to
-`max_len(dtype)` take the kernels; longer axes, CPU tensors and other dtypes take a composition of `torch.fft`
-calls on the tensor's device (`_torch_axis`), which applies the same matrices.
+into the result, the rest in place on the result, whichever kernel an axis takes.  Axes longer than
+`mm_max_len(dtype)`, CPU tensors and other dtypes take a composition of `torch.fft` calls on the tensor's device
+(`_torch_axis`), which applies the same matrices.
 
 The inverses are the forward transform with norm (forward <-> backward) and type (2 <-> 3) flipped.  Half
 precision promotes to float32, integers to float64, as upstream.  DCT-I of a single point has no definition
@@ -29,16 +32,27 @@ _KERNEL_DTYPES = {torch.float32: _lib.F32, torch.float64: _lib.F64}
 _FLIPNORM = {'backward': 'forward', 'forward': 'backward', 'ortho': 'ortho', 'ortho_scipy': 'ortho_scipy'}
 _FLIPTYPE = {1: 1, 2: 3, 3: 2}
 _max_len = {}
+_mm_max_len = {}
 
 
 def max_len(dtype):
-    """longest axis the kernels serve for `dtype` (0 for a dtype they do not serve)"""
+    """longest axis the lane kernels serve for `dtype` (0 for a dtype they do not serve)"""
     code = _KERNEL_DTYPES.get(dtype)
     if code is None:
         return 0
     if code not in _max_len:
         _max_len[code] = int(_lib.lib().nfm_rt_max_len(code))
     return _max_len[code]
+
+
+def mm_max_len(dtype):
+    """longest axis routed to the matrix-core kernel for `dtype` (0 for a dtype it does not serve)"""
+    code = _KERNEL_DTYPES.get(dtype)
+    if code is None:
+        return 0
+    if code not in _mm_max_len:
+        _mm_max_len[code] = int(_lib.lib().nfm_rt_mm_max_len(code))
+    return _mm_max_len[code]
 
 
 def _plan(kind, type, norm, N, transpose):
@@ -145,8 +159,13 @@ def _layout(x):
     return x.contiguous(), None
 
 
-def _use_kernel(x, N, force_torch):
-    return not force_torch and x.is_cuda and 0 < N <= max_len(x.dtype)
+def _route(x, N, force_torch):
+    """who transforms an axis of length N of x: 'lane' (nfm_rt_transform), 'mm' (nfm_rt_transform_mm) or 'torch'"""
+    if force_torch or not x.is_cuda or N <= 0:
+        return 'torch'
+    if N <= max_len(x.dtype):
+        return 'lane'
+    return 'mm' if N <= mm_max_len(x.dtype) else 'torch'
 
 
 def _apply(x, dims, kind, type, norm, transpose, force_torch=False):
@@ -162,11 +181,13 @@ def _apply(x, dims, kind, type, norm, transpose, force_torch=False):
     cur, out = xp, None
     for d in dims:
         N = cur.shape[d]
-        if _use_kernel(cur, N, force_torch):
+        route = _route(cur, N, force_torch)
+        if route != 'torch':
             if out is None:
                 out = torch.empty_like(cur, memory_format=torch.contiguous_format)
             outer, _, inner = _view(cur, d)
-            call(_lib.lib().nfm_rt_transform, cur.device, _KERNEL_DTYPES[cur.dtype], kind, type,
+            fn = _lib.lib().nfm_rt_transform if route == 'lane' else _lib.lib().nfm_rt_transform_mm
+            call(fn, cur.device, _KERNEL_DTYPES[cur.dtype], kind, type,
                  _lib.RT_NORMS[norm], int(transpose), N, outer, inner, cur.data_ptr(), out.data_ptr())
             cur = out
         else:

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Worst observed fraction of the error bound of the real-transform kernels, per kind, type and N (over the four
+"""Worst observed fraction of the error bound of the real-transform kernels (the lane kernels up to `max_len`, the
+matrix-core kernel from there to `mm_max_len`), per kind, type and N (over the four
 norms, both transpose settings, unit impulses and dense random lines, lines along the first and the last axis).
 The bound is tests/_realtransforms_ref.bound: (N + 6) eps sum |M_kn| |x_n| + the smallest normal number.
 
@@ -25,10 +26,10 @@ def main():
     lines = ['| kind | type | N | float32 | float64 |', '|---|---|---|---|---|']
     for kind in R.KINDS:
         for type in R.TYPES:
-            for N in (2, 3, 8, 17, 32, 33, 64):
+            for N in (2, 3, 8, 17, 32, 33, 64, 65, 128, 129, 182, 218, 256):
                 row = []
                 for dtype, td in ((np.float32, torch.float32), (np.float64, torch.float64)):
-                    if N > RT.max_len(td):
+                    if N > max(RT.max_len(td), RT.mm_max_len(td)):
                         row.append('-')
                         continue
                     worst = 0.0
