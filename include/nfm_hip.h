@@ -489,6 +489,37 @@ int nfm_svd_solve_host(int dtype, int M, int N, int K, int flags, double rcond, 
  * outside 1..NFM_SVD_MAX_DIM */
 int nfm_svd_max_cols(int dtype, int M, int N);
 
+/* X = A^+ B for one TALL M x N matrix and one M x K matrix of right-hand sides per batch element: the least-squares
+ * solves of `lmdiv` / `solvevec` / `rmdiv` with more rows than nfm_svd_solve holds.  X (N x K) = pinv(A, rcond) B:
+ * the minimum-norm least-squares solution, singular values sigma <= rcond sigma_max dropped (`torch.linalg.pinv`'s
+ * reading of rcond; the reference turns every non-square system into `pinv`, so there is no flags argument).  The
+ * M rows of [A | B] stream once past an N x N triangle R and Q^T B held in the lane's registers (Givens rotations;
+ * every record scaled by a running power of two, so any finite record is in range), and the Jacobi routine of
+ * nfm_svd_solve finishes on R, which has the singular values of A: one read of A and B, one write of X, one launch,
+ * no workspace, no host sync.  Rank deficiency is resolved by rcond alone.  A zero record gives X = 0; a NaN or inf
+ * in a record gives NaN for that record only.
+ * N in 1..8; M in N..NFM_LSTSQ_MAX_ROWS; K in 1..nfm_lstsq_max_cols(dtype, N) (solve B in blocks of columns beyond).
+ * The operand fields are those of nfm_svd_solve; every layout is read in place.  `out` must not alias `a` or `b`.
+ * Status precedence: NFM_EDTYPE; NFM_EINVAL negative count; NFM_ESIZE n_outer; NFM_ESIZE N or K outside 1..8;
+ * NFM_ESIZE M < N or M > NFM_LSTSQ_MAX_ROWS; NFM_EINVAL an rcond that is negative or NaN; NFM_ESIZE K above the cap;
+ * then a, b, out in this order: NFM_EINVAL for a null pointer with a non-empty batch, NFM_EALIGN.  An empty batch
+ * with null pointers succeeds without a launch. */
+#define NFM_LSTSQ_MAX_ROWS 4096
+int nfm_lstsq_solve(int dtype, int M, int N, int K, double rcond, int64_t n_outer, int64_t n_inner,
+                    const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                    const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                    void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream);
+/* the same per-record routine on the calling thread, for records in host memory.  Same arguments and status codes;
+ * on success the return value is the largest number of sweeps the finishing Jacobi loop took (0 for an empty batch
+ * and for N == 1). */
+int nfm_lstsq_solve_host(int dtype, int M, int N, int K, double rcond, int64_t n_outer, int64_t n_inner,
+                         const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                         const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                         void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc);
+/* largest K one nfm_lstsq_solve call takes at N columns; NFM_EDTYPE / NFM_ESIZE for an unknown dtype / an N outside
+ * 1..8 */
+int nfm_lstsq_max_cols(int dtype, int N);
+
 /* --------------------------------------------------------- realtransforms ---- */
 
 /* Discrete cosine / sine transforms of types I, II, III along the middle axis of a contiguous (outer, N, inner)

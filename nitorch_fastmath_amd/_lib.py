@@ -26,6 +26,7 @@ SP_BESSELI, SP_BESSELI_BWD, SP_RATIO, SP_RATIO_BWD, SP_MVDIGAMMA, SP_MVDIGAMMA_B
 SP_MAX_N = 8
 SOLVE_LU, SOLVE_CHOL, SOLVE_MAX_DIM = 0, 1, 8    # include/nfm_hip.h: NFM_SOLVE_*
 SVD_PLAIN, SVD_PINV, SVD_MAX_DIM, SVD_MAX_SWEEPS = 0, 1, 8, 16    # include/nfm_hip.h: NFM_SVD_*
+LSTSQ_MAX_ROWS, LSTSQ_MAX_N = 4096, 8    # include/nfm_hip.h: NFM_LSTSQ_MAX_ROWS, the N of nfm_lstsq_solve
 # include/nfm_hip.h: NFM_RT_*
 RT_DCT, RT_DST = 0, 1
 RT_NORMS = {'backward': 0, 'forward': 1, 'ortho': 2, 'ortho_scipy': 3}
@@ -77,6 +78,9 @@ SIGNATURES = {
     'nfm_svd_solve': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
     'nfm_svd_solve_host': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64],
     'nfm_svd_max_cols': [_i, _i, _i],
+    'nfm_lstsq_solve': [_i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
+    'nfm_lstsq_solve_host': [_i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64],
+    'nfm_lstsq_max_cols': [_i, _i],
     'nfm_rt_transform': [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp],
     'nfm_rt_transform_host': [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp],
     'nfm_rt_max_len': [_i],

@@ -4,9 +4,13 @@
 `lmdiv`, `rmdiv`, `solvevec` and `inv` on matrices of at most 8 rows and columns run one lane-per-system HIP
 kernel: `nfm_sugar_solve` for `lu` / `chol` on square matrices (Gaussian elimination with partial pivoting on
 `[A | B]`, or Cholesky from the lower triangle), `nfm_svd_solve` for `svd` / `pinv` and for every non-square
-system (one-sided Jacobi SVD on the rows of `[A | B]`: least squares for m > n, minimum norm for m < n).  The
+system (one-sided Jacobi SVD on the rows of `[A | B]`: least squares for m > n, minimum norm for m < n).  Tall
+least-squares systems -- more than 8 rows (up to 4096), at most 8 columns: a model fit per voxel -- run
+`nfm_lstsq_solve`: the rows of `[A | B]` stream once past an n x n triangle in the lane's registers (Givens
+rotations) and the same Jacobi routine finishes on it, `pinv(a, rcond) @ b` in one launch.  The
 reference runs torch's batched LU / SVD, which are slow on tiny matrices.  Transposed, broadcast, padded and
-channel-first operands are read in place.  Orders above 8, and `svd` / `pinv` calls that need a gradient, take
+channel-first operands are read in place.  More than 8 columns, square orders above 8, `inv` of a tall matrix,
+and `svd` / `pinv` / non-square calls that need a gradient, take
 the reference's own torch composition on the device; the remaining names (`kron2`, `outer`, `trace`, `dot`,
 `mdot`, `is_orthonormal`, `round`) are torch compositions on the device, without a kernel.
 
@@ -38,8 +42,10 @@ MAX_ORDER = _lib.SOLVE_MAX_DIM
 _FLAGS = {'lu': _lib.SOLVE_LU, 'chol': _lib.SOLVE_CHOL}
 _SVD_FLAGS = {'svd': _lib.SVD_PLAIN, 'pinv': _lib.SVD_PINV}
 SVD_MAX_DIM = _lib.SVD_MAX_DIM
+LSTSQ_MAX_ROWS, LSTSQ_MAX_N = _lib.LSTSQ_MAX_ROWS, _lib.LSTSQ_MAX_N
 _caps = {}
 _svd_caps = {}
+_lstsq_caps = {}
 
 
 def max_cols(dtype, n):
@@ -56,6 +62,14 @@ def svd_max_cols(dtype, m, n):
     if key not in _svd_caps:
         _svd_caps[key] = int(_lib.lib().nfm_svd_max_cols(dtype_code(dtype), m, n))
     return _svd_caps[key]
+
+
+def lstsq_max_cols(dtype, n):
+    """Columns of `b` one launch takes for a tall system of `n` columns (the library's table, `nfm_lstsq_max_cols`)."""
+    key = (dtype, n)
+    if key not in _lstsq_caps:
+        _lstsq_caps[key] = int(_lib.lib().nfm_lstsq_max_cols(dtype_code(dtype), n))
+    return _lstsq_caps[key]
 
 
 def _method(method, a):
@@ -169,6 +183,44 @@ def _svd_solve(a, b, flag, rcond, out=None):
     return out
 
 
+def _lstsq_ok(a):
+    return SVD_MAX_DIM < a.shape[-2] <= LSTSQ_MAX_ROWS and 0 < a.shape[-1] <= LSTSQ_MAX_N
+
+
+def _lstsq_launch(dev, dtype, m, n, k, rcond, a, b, out):
+    """one nfm_lstsq_solve call; a / b / out share their batch dims (views)"""
+    bt = Batch(out.shape[:-2], [a, b, out], [2, 2, 2])
+    o = bt.operands
+    call(_lib.lib().nfm_lstsq_solve, dev, dtype_code(dtype), m, n, k, float(rcond), bt.n_outer, bt.n_inner,
+         *_fields(o[0]), *_fields(o[1]), *_fields(o[2]))
+    bt.finish()
+
+
+def _lstsq_solve(a, b, rcond, out=None):
+    """X = pinv(a, rcond) b on the streaming kernel: a (..., m, n), 8 < m <= 4096, n <= 8; b (..., m, k); forward
+    only.  Column blocks as in `_solve`."""
+    dev, dtype = a.device, a.dtype
+    m, n = a.shape[-2:]
+    k = b.shape[-1]
+    batch = broadcast_shapes(a.shape[:-2], b.shape[:-2])
+    shape = tuple(batch) + (n, k)
+    if out is None:
+        out = _like(b, shape, dtype, dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev:
+        raise ValueError(f'out= must be a {dtype} tensor of shape {shape} on {dev}')
+    if out.numel() == 0:
+        return out
+    a, b = expand_batch(batch, a, 2), expand_batch(batch, b, 2)
+    cap = lstsq_max_cols(dtype, n)
+    for c0 in range(0, k, cap):
+        c1 = min(c0 + cap, k)
+        if c0 == 0 and c1 == k:
+            _lstsq_launch(dev, dtype, m, n, k, rcond, a, b, out)
+        else:
+            _lstsq_launch(dev, dtype, m, n, c1 - c0, rcond, a, b[..., c0:c1], out[..., c0:c1])
+    return out
+
+
 def _check_out(out, *tensors):
     if out is not None and torch.is_grad_enabled() and any(t.requires_grad for t in tensors + (out,)):
         raise RuntimeError('out= is not supported for tensors that require grad')
@@ -205,14 +257,24 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
     method : `{'lu', 'chol', 'svd', 'pinv'}`; non-square `a` always takes `pinv`.
     `a` with m, n <= 8 runs a HIP kernel: elimination (`lu`), Cholesky from the lower triangle only (`chol`), or
     the Jacobi SVD (`svd`, `pinv`, every non-square `a`; forward only -- with a gradient: the torch composition).
-    `pinv` drops the singular values `<= rcond sigma_max`; `svd` divides by every one of them."""
+    `pinv` drops the singular values `<= rcond sigma_max`; `svd` divides by every one of them.
+    A tall `a` with 8 < m <= 4096 rows and n <= 8 columns runs the streaming least-squares kernel
+    (`nfm_lstsq_solve`; forward only): exactly `pinv(a, rcond) @ b`, the minimum-norm least-squares solution.
+    Rank deficiency is resolved by `rcond` alone, as in `torch.linalg.pinv`: at the default `rcond = 1e-15` a
+    numerically rank-deficient float32 record is as meaningless here as it is there -- pass an `rcond` of the
+    order of the data's precision for such fits.  Wide systems with more than 8 columns take the torch
+    composition."""
     dev, dtype, (a, b) = prepare(None, a, b, grad_ok=True)
     _check_out(out, a, b)
     method = _method(method, a)
     if b.shape[-2] != a.shape[-2]:
         raise ValueError(f'system {tuple(a.shape[-2:])} and right-hand side {tuple(b.shape[-2:])} do not match')
     if method in _SVD_FLAGS:
-        if not _svd_ok(a) or needs_grad(a, b):
+        if needs_grad(a, b):
+            return _torch_lmdiv(a, b, method, rcond, out)
+        if method == 'pinv' and _lstsq_ok(a):
+            return _lstsq_solve(a, b, rcond, out)
+        if not _svd_ok(a):
             return _torch_lmdiv(a, b, method, rcond, out)
         return _svd_solve(a, b, _SVD_FLAGS[method], rcond, out)
     if a.shape[-1] > MAX_ORDER or a.shape[-1] == 0:
@@ -285,7 +347,9 @@ def matvec(mat, vec, out=None):
 
 
 def solvevec(mat, vec, method='lu', rcond=1e-15, out=None):
-    """Left matrix-vector division `A^-1 b` (sugar.py:290-341): `lmdiv` with one column, on views."""
+    """Left matrix-vector division `A^-1 b` (sugar.py:290-341): `lmdiv` with one column, on views -- a tall `mat`
+    (8 < m <= 4096 rows, n <= 8 columns) is the least-squares fit `pinv(mat, rcond) @ vec` on the streaming kernel,
+    rank deficiency resolved by `rcond` alone."""
     vec = torch.as_tensor(vec)
     return lmdiv(mat, vec.unsqueeze(-1), method=method, rcond=rcond,
                  out=None if out is None else out.unsqueeze(-1)).squeeze(-1)
