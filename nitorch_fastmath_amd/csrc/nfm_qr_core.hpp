@@ -967,6 +967,10 @@ __device__ __forceinline__ void qr_fast_band1(T (&d)[Dim<NT>::MAX], T (&e)[Dim<N
             int iters = max_iter;
             if (m == 2 && max_iter > 0)
                 if (jacobi2_fast1<T, NT, WITH_U>(d, e, u, n)) iters = 0;
+            // an off-diagonal that is an exact zero already (diagonal / block-diagonal input, padding lanes):
+            // d[m-1] is an eigenvalue as it stands, and a sweep would only move the diagonal by an ulp,
+            // (d - sigma) + sigma.  Nothing else changes: a lane with e != 0 iterates as before.
+            if (e[m - 2] == T(0)) iters = 0;
             T ratio_prev = T(0);
             for (int it = 0; it < iters; ++it) {
                 const T sigma = wilkinson_fast1(d[m - 2], d[m - 1], e[m - 2]);

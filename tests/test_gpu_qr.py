@@ -153,7 +153,8 @@ def check_eigenpairs(sym, ev, evec, n, dn):
 def test_vs_oracle(dev, oracle, dn, n):
     """seeded inputs, every order (orders > 5 raise upstream), ragged batch.  The kernels run the
     oracle's operation order, so everything except the fast float32 sweeps is held to TOL against
-    the oracle at EVERY order (measured: bit-identical)."""
+    the oracle at EVERY order (measured: bit-identical).  Orders 9..16 are run one by one, on a thousand
+    records and in both kernel forms, by test_gpu_qr_large_orders.py (profiles/qr_large_orders_parity.md)."""
     dtype = np.float32 if dn == 'f32' else np.float64
     tol = TOL[dn]
     nb = 777 if n <= 8 else 130
