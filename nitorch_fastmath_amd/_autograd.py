@@ -267,7 +267,7 @@ class LmdivFn(torch.autograd.Function):
     def forward(ctx, a, b, flag):
         from . import sugar as S
         with torch.no_grad():
-            x = S._solve(a, b, flag)
+            x = S._kernel_solve(S._SQUARE, a, b, flag=flag)
         ctx.flag = flag
         ctx.save_for_backward(a, x)
         ctx.shapes = (a.shape, b.shape)
@@ -278,7 +278,7 @@ class LmdivFn(torch.autograd.Function):
     def backward(ctx, g):
         from . import sugar as S
         a, x = ctx.saved_tensors
-        gb = S._solve(a if ctx.flag == _lib.SOLVE_CHOL else a.transpose(-1, -2), g, ctx.flag)
+        gb = S._kernel_solve(S._SQUARE, a if ctx.flag == _lib.SOLVE_CHOL else a.transpose(-1, -2), g, flag=ctx.flag)
         ga = None
         if ctx.needs_input_grad[0]:
             ga = _sum_to(-_small_matmul(gb, x.transpose(-1, -2)), ctx.shapes[0])

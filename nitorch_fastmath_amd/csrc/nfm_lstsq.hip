@@ -16,6 +16,7 @@
 //   3. lstsq_lane_kernel with any other strides (a.mT, broadcast, padded records): the same per-lane loads.
 // X is N K values per record and goes out with direct stores at the strides of `out`.
 #include "nfm_lstsq_ops.hpp"
+#include "nfm_solve_entry.hpp"
 
 namespace nfm {
 
@@ -230,9 +231,7 @@ static int lstsq_host_loop(int M, int64_t no, int64_t ni, const nfm_operand *a, 
             T x[N][K];
             const int sweeps = lstsq_finish<T, N, K>(st, x, T(rcond * rcond));
             most = sweeps > most ? sweeps : most;
-            T *po = static_cast<T *>(out->ptr) + o * out->stride_outer + i * out->stride_inner;
-            for (int r = 0; r < N; ++r)
-                for (int c = 0; c < K; ++c) po[r * out->stride_row + c * out->stride_col] = x[r][c];
+            host_scatter<T>(out, o, i, N, K, &x[0][0]);
         }
     return most;
 }
@@ -291,17 +290,16 @@ using namespace nfm;
 static int lstsq_entry(int dtype, int M, int N, int K, double rcond, int64_t n_outer, int64_t n_inner,
                        const nfm_operand &oa, const nfm_operand &ob, const nfm_operand &oo, int host, void *stream)
 {
-    int rc = check_batch(dtype, n_outer, n_inner, {N, K}, kLstsqMaxN);
+    const int rc = check_batch(dtype, n_outer, n_inner, {N, K}, kLstsqMaxN);
     if (rc) return rc;
     if (M < N || M > kLstsqMaxRows) return NFM_ESIZE;
     if (!(rcond >= 0.0)) return NFM_EINVAL;
-    if (K > lstsq_max_k(dtype == NFM_F64, N)) return NFM_ESIZE;
-    if ((rc = check_operands(dtype, n_outer, n_inner, {&oa, &ob, &oo}))) return rc;
-    if (n_outer == 0 || n_inner == 0) return NFM_OK;
+    const SolveRhs rhs = check_rhs(dtype, n_outer, n_inner, K, lstsq_max_k(dtype == NFM_F64, N), 0, oa, ob, oo);
+    if (!rhs.launch) return rhs.rc;
     const int part = (dtype == NFM_F64 ? 8 : 0) + N - 1;
     return switch_order<16>(part + 1, NFM_ESIZE, [&](auto p) {
         constexpr int P = p;
-        return lstsq_part<P - 1>(M, K, n_outer, n_inner, &oa, &ob, &oo, rcond, host, stream);
+        return lstsq_part<P - 1>(M, K, n_outer, n_inner, &oa, rhs.b, &oo, rcond, host, stream);
     });
 }
 
@@ -309,9 +307,7 @@ extern "C" {
 
 int nfm_lstsq_max_cols(int dtype, int N)
 {
-    if (dtype != NFM_F32 && dtype != NFM_F64) return NFM_EDTYPE;
-    if (N < 1 || N > kLstsqMaxN) return NFM_ESIZE;
-    return lstsq_max_k(dtype == NFM_F64, N);
+    return max_cols_answer(dtype, {N}, kLstsqMaxN, lstsq_max_k(dtype == NFM_F64, N));
 }
 
 int nfm_lstsq_solve(int dtype, int M, int N, int K, double rcond, int64_t n_outer, int64_t n_inner,
@@ -319,8 +315,8 @@ int nfm_lstsq_solve(int dtype, int M, int N, int K, double rcond, int64_t n_oute
                     const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
                     void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream)
 {
-    return lstsq_entry(dtype, M, N, K, rcond, n_outer, n_inner, {const_cast<void *>(a), a_so, a_si, a_sr, a_sc},
-                       {const_cast<void *>(b), b_so, b_si, b_sr, b_sc}, {out, o_so, o_si, o_sr, o_sc}, 0, stream);
+    return lstsq_entry(dtype, M, N, K, rcond, n_outer, n_inner, flat_operand(a, a_so, a_si, a_sr, a_sc),
+                       flat_operand(b, b_so, b_si, b_sr, b_sc), flat_operand(out, o_so, o_si, o_sr, o_sc), 0, stream);
 }
 
 int nfm_lstsq_solve_host(int dtype, int M, int N, int K, double rcond, int64_t n_outer, int64_t n_inner,
@@ -328,8 +324,8 @@ int nfm_lstsq_solve_host(int dtype, int M, int N, int K, double rcond, int64_t n
                          const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
                          void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc)
 {
-    return lstsq_entry(dtype, M, N, K, rcond, n_outer, n_inner, {const_cast<void *>(a), a_so, a_si, a_sr, a_sc},
-                       {const_cast<void *>(b), b_so, b_si, b_sr, b_sc}, {out, o_so, o_si, o_sr, o_sc}, 1, nullptr);
+    return lstsq_entry(dtype, M, N, K, rcond, n_outer, n_inner, flat_operand(a, a_so, a_si, a_sr, a_sc),
+                       flat_operand(b, b_so, b_si, b_sr, b_sc), flat_operand(out, o_so, o_si, o_sr, o_sc), 1, nullptr);
 }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 // grid of fully unrolled sweeps builds in parallel:
 // PART = dtype * 16 + (M - 1) * 2 + half; half h holds N = 4h + 1 .. 4h + 4, every K = 1..svd_max_k.
 #include "nfm_svd_ops.hpp"
+#include "nfm_solve_entry.hpp"
 
 namespace nfm {
 
@@ -34,19 +35,11 @@ static int svd_host_loop(int64_t no, int64_t ni, const nfm_operand *a, const nfm
     for (int64_t o = 0; o < no; ++o)
         for (int64_t i = 0; i < ni; ++i) {
             T ra[M * N], rb[M * K], ro[N * K];
-            const T *pa = static_cast<const T *>(a->ptr) + o * a->stride_outer + i * a->stride_inner;
-            for (int r = 0; r < M; ++r)
-                for (int c = 0; c < N; ++c) ra[r * N + c] = pa[r * a->stride_row + c * a->stride_col];
-            if constexpr (!IDENT) {
-                const T *pb = static_cast<const T *>(b->ptr) + o * b->stride_outer + i * b->stride_inner;
-                for (int r = 0; r < M; ++r)
-                    for (int c = 0; c < K; ++c) rb[r * K + c] = pb[r * b->stride_row + c * b->stride_col];
-            }
+            host_gather<T>(a, o, i, M, N, ra);
+            if constexpr (!IDENT) host_gather<T>(b, o, i, M, K, rb);
             const int sweeps = svd_solve_flat<T, M, N, K, IDENT>(ra, rb, ro, prm);
             most = sweeps > most ? sweeps : most;
-            T *po = static_cast<T *>(out->ptr) + o * out->stride_outer + i * out->stride_inner;
-            for (int r = 0; r < N; ++r)
-                for (int c = 0; c < K; ++c) po[r * out->stride_row + c * out->stride_col] = ro[r * K + c];
+            host_scatter<T>(out, o, i, N, K, ro);
         }
     return most;
 }
@@ -92,23 +85,17 @@ using namespace nfm;
 static int svd_entry(int dtype, int M, int N, int K, int flags, double rcond, int64_t n_outer, int64_t n_inner,
                      const nfm_operand &oa, const nfm_operand &ob, const nfm_operand &oo, int host, void *stream)
 {
-    int rc = check_batch(dtype, n_outer, n_inner, {M, N, K}, kSvdMaxDim);
+    const int rc = check_batch(dtype, n_outer, n_inner, {M, N, K}, kSvdMaxDim);
     if (rc) return rc;
     if (flags != NFM_SVD_PLAIN && flags != NFM_SVD_PINV) return NFM_EINVAL;
     if (!(rcond >= 0.0)) return NFM_EINVAL;
-    const bool empty = n_outer == 0 || n_inner == 0;
-    // (an empty batch carries null pointers throughout: B is then taken as present)
-    const bool identity = ob.ptr == nullptr && !empty;
-    if (identity && K != M) return NFM_EINVAL;
-    if (!identity && K > svd_max_k(dtype == NFM_F64, M, N)) return NFM_ESIZE;
-    if ((rc = check_operands(dtype, n_outer, n_inner, {&oa, {&ob, !identity}, &oo}))) return rc;
-    if (empty) return NFM_OK;
-    const nfm_operand *pb = identity ? nullptr : &ob;
+    const SolveRhs rhs = check_rhs(dtype, n_outer, n_inner, K, svd_max_k(dtype == NFM_F64, M, N), M, oa, ob, oo);
+    if (!rhs.launch) return rhs.rc;
     const SvdParams prm{flags == NFM_SVD_PINV, rcond};
     const int part = (dtype == NFM_F64 ? 16 : 0) + (M - 1) * 2 + (N > 4);
     return switch_order<32>(part + 1, NFM_ESIZE, [&](auto p) {
         constexpr int P = p;
-        return svd_part<P - 1>(N, K, n_outer, n_inner, &oa, pb, &oo, prm, host, stream);
+        return svd_part<P - 1>(N, K, n_outer, n_inner, &oa, rhs.b, &oo, prm, host, stream);
     });
 }
 
@@ -116,9 +103,7 @@ extern "C" {
 
 int nfm_svd_max_cols(int dtype, int M, int N)
 {
-    if (dtype != NFM_F32 && dtype != NFM_F64) return NFM_EDTYPE;
-    if (M < 1 || M > kSvdMaxDim || N < 1 || N > kSvdMaxDim) return NFM_ESIZE;
-    return svd_max_k(dtype == NFM_F64, M, N);
+    return max_cols_answer(dtype, {M, N}, kSvdMaxDim, svd_max_k(dtype == NFM_F64, M, N));
 }
 
 int nfm_svd_solve(int dtype, int M, int N, int K, int flags, double rcond, int64_t n_outer, int64_t n_inner,
@@ -126,8 +111,8 @@ int nfm_svd_solve(int dtype, int M, int N, int K, int flags, double rcond, int64
                   const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
                   void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream)
 {
-    return svd_entry(dtype, M, N, K, flags, rcond, n_outer, n_inner, {const_cast<void *>(a), a_so, a_si, a_sr, a_sc},
-                     {const_cast<void *>(b), b_so, b_si, b_sr, b_sc}, {out, o_so, o_si, o_sr, o_sc}, 0, stream);
+    return svd_entry(dtype, M, N, K, flags, rcond, n_outer, n_inner, flat_operand(a, a_so, a_si, a_sr, a_sc),
+                     flat_operand(b, b_so, b_si, b_sr, b_sc), flat_operand(out, o_so, o_si, o_sr, o_sc), 0, stream);
 }
 
 int nfm_svd_solve_host(int dtype, int M, int N, int K, int flags, double rcond, int64_t n_outer, int64_t n_inner,
@@ -135,8 +120,8 @@ int nfm_svd_solve_host(int dtype, int M, int N, int K, int flags, double rcond, 
                        const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
                        void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc)
 {
-    return svd_entry(dtype, M, N, K, flags, rcond, n_outer, n_inner, {const_cast<void *>(a), a_so, a_si, a_sr, a_sc},
-                     {const_cast<void *>(b), b_so, b_si, b_sr, b_sc}, {out, o_so, o_si, o_sr, o_sc}, 1, nullptr);
+    return svd_entry(dtype, M, N, K, flags, rcond, n_outer, n_inner, flat_operand(a, a_so, a_si, a_sr, a_sc),
+                     flat_operand(b, b_so, b_si, b_sr, b_sc), flat_operand(out, o_so, o_si, o_sr, o_sc), 1, nullptr);
 }
 
 } // extern "C"

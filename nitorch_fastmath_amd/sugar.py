@@ -34,6 +34,7 @@ __all__ = [
     'is_orthonormal',
     'round',
 ]
+import collections
 import torch
 from . import _lib
 from ._dispatch import Batch, broadcast_shapes, call, dtype_code, expand_batch, needs_grad, prepare
@@ -43,33 +44,43 @@ _FLAGS = {'lu': _lib.SOLVE_LU, 'chol': _lib.SOLVE_CHOL}
 _SVD_FLAGS = {'svd': _lib.SVD_PLAIN, 'pinv': _lib.SVD_PINV}
 SVD_MAX_DIM = _lib.SVD_MAX_DIM
 LSTSQ_MAX_ROWS, LSTSQ_MAX_N = _lib.LSTSQ_MAX_ROWS, _lib.LSTSQ_MAX_N
+
+# One kernel family behind `lmdiv` / `inv`, for an (m, n) system and k columns of b:
+#   entry    : its C entry point, `entry(dtype code, *scalars(m, n, k, flag, rcond), n_outer, n_inner, a, b, out,
+#              stream)`
+#   cap      : its column-cap query, `cap(dtype code, *dims(m, n))`
+#   identity : the axis of `a` that is the k of a call with b=None (the identity), None when b is required
+_Family = collections.namedtuple('_Family', 'entry scalars cap dims identity')
+_SQUARE = _Family('nfm_sugar_solve', lambda m, n, k, flag, rcond: (n, k, flag),
+                  'nfm_sugar_max_cols', lambda m, n: (n,), -1)
+_SVD = _Family('nfm_svd_solve', lambda m, n, k, flag, rcond: (m, n, k, flag, float(rcond)),
+               'nfm_svd_max_cols', lambda m, n: (m, n), -2)
+_LSTSQ = _Family('nfm_lstsq_solve', lambda m, n, k, flag, rcond: (m, n, k, float(rcond)),
+                 'nfm_lstsq_max_cols', lambda m, n: (n,), None)
 _caps = {}
-_svd_caps = {}
-_lstsq_caps = {}
+
+
+def _cap(query, dtype, *dims):
+    """the library's answer to the column-cap query `query`, asked once per (dtype, dims)"""
+    key = (query, dtype, dims)
+    if key not in _caps:
+        _caps[key] = int(getattr(_lib.lib(), query)(dtype_code(dtype), *dims))
+    return _caps[key]
 
 
 def max_cols(dtype, n):
     """Columns of `b` one launch takes at order `n` (the library's table, `nfm_sugar_max_cols`)."""
-    key = (dtype, n)
-    if key not in _caps:
-        _caps[key] = int(_lib.lib().nfm_sugar_max_cols(dtype_code(dtype), n))
-    return _caps[key]
+    return _cap(_SQUARE.cap, dtype, n)
 
 
 def svd_max_cols(dtype, m, n):
     """Columns of `b` one launch takes for an `m x n` system (the library's table, `nfm_svd_max_cols`)."""
-    key = (dtype, m, n)
-    if key not in _svd_caps:
-        _svd_caps[key] = int(_lib.lib().nfm_svd_max_cols(dtype_code(dtype), m, n))
-    return _svd_caps[key]
+    return _cap(_SVD.cap, dtype, m, n)
 
 
 def lstsq_max_cols(dtype, n):
     """Columns of `b` one launch takes for a tall system of `n` columns (the library's table, `nfm_lstsq_max_cols`)."""
-    key = (dtype, n)
-    if key not in _lstsq_caps:
-        _lstsq_caps[key] = int(_lib.lib().nfm_lstsq_max_cols(dtype_code(dtype), n))
-    return _lstsq_caps[key]
+    return _cap(_LSTSQ.cap, dtype, n)
 
 
 def _method(method, a):
@@ -87,26 +98,13 @@ def _fields(op):
     return op.ptr, op.stride_outer, op.stride_inner, op.stride_row, op.stride_col
 
 
-def _launch(dev, dtype, n, k, flag, a, b, out):
-    """one nfm_sugar_solve call; a / b / out share their batch dims (views); b None: the identity"""
-    batch = out.shape[:-2]
+def _launch(family, dev, dtype, scalars, a, b, out):
+    """one call of the family's entry point; a / b / out share their batch dims (views); b None: the identity"""
     tensors = [a, out] if b is None else [a, b, out]
-    bt = Batch(batch, tensors, [2] * len(tensors))
+    bt = Batch(out.shape[:-2], tensors, [2] * len(tensors))
     o = bt.operands
     fb = (None, 0, 0, 0, 0) if b is None else _fields(o[1])
-    call(_lib.lib().nfm_sugar_solve, dev, dtype_code(dtype), n, k, flag, bt.n_outer, bt.n_inner,
-         *_fields(o[0]), *fb, *_fields(o[-1]))
-    bt.finish()
-
-
-def _svd_launch(dev, dtype, m, n, k, flag, rcond, a, b, out):
-    """one nfm_svd_solve call; a / b / out share their batch dims (views); b None: the identity"""
-    batch = out.shape[:-2]
-    tensors = [a, out] if b is None else [a, b, out]
-    bt = Batch(batch, tensors, [2] * len(tensors))
-    o = bt.operands
-    fb = (None, 0, 0, 0, 0) if b is None else _fields(o[1])
-    call(_lib.lib().nfm_svd_solve, dev, dtype_code(dtype), m, n, k, flag, float(rcond), bt.n_outer, bt.n_inner,
+    call(getattr(_lib.lib(), family.entry), dev, dtype_code(dtype), *scalars, bt.n_outer, bt.n_inner,
          *_fields(o[0]), *fb, *_fields(o[-1]))
     bt.finish()
 
@@ -121,13 +119,21 @@ def _like(like, shape, dtype, dev):
     return torch.empty(shape, dtype=dtype, device=dev)
 
 
-def _solve(a, b, flag, out=None):
-    """X = a^-1 b on the kernel: a (..., n, n), n <= 8; b (..., n, k) or None (identity); forward only.
-    More columns than one launch takes: one launch per block of columns, on views of b and out."""
+def _blocks(k, cap):
+    """the column blocks [c0, c1) of k columns at `cap` columns per launch"""
+    return [(c0, min(c0 + cap, k)) for c0 in range(0, k, cap)]
+
+
+def _kernel_solve(family, a, b, out=None, flag=None, rcond=None):
+    """X = a^-1 b (a^+ b) on the kernels of `family`: a (..., m, n) in the family's range; b (..., m, k), or None
+    for the identity where the family has one; forward only.  A k that fits one launch is one launch on a, b and
+    out themselves; more columns are one launch per block of columns, on views of b and out."""
     dev, dtype = a.device, a.dtype
-    n = a.shape[-1]
-    k = n if b is None else b.shape[-1]
-    batch = a.shape[:-2] if b is None else broadcast_shapes(a.shape[:-2], b.shape[:-2])
+    m, n = a.shape[-2:]
+    if b is None:
+        k, batch = a.shape[family.identity], a.shape[:-2]
+    else:
+        k, batch = b.shape[-1], broadcast_shapes(a.shape[:-2], b.shape[:-2])
     shape = tuple(batch) + (n, k)
     if out is None:
         out = _like(b, shape, dtype, dev)
@@ -136,17 +142,15 @@ def _solve(a, b, flag, out=None):
     if out.numel() == 0:
         return out
     a = expand_batch(batch, a, 2)
-    if b is None:
-        _launch(dev, dtype, n, n, flag, a, None, out)
-        return out
-    b = expand_batch(batch, b, 2)
-    cap = max_cols(dtype, n)
-    for c0 in range(0, k, cap):
-        c1 = min(c0 + cap, k)
-        if c0 == 0 and c1 == k:
-            _launch(dev, dtype, n, k, flag, a, b, out)
-        else:
-            _launch(dev, dtype, n, c1 - c0, flag, a, b[..., c0:c1], out[..., c0:c1])
+    if b is not None:
+        b = expand_batch(batch, b, 2)
+        cap = _cap(family.cap, dtype, *family.dims(m, n))
+        if k > cap:
+            for c0, c1 in _blocks(k, cap):
+                _launch(family, dev, dtype, family.scalars(m, n, c1 - c0, flag, rcond), a, b[..., c0:c1],
+                        out[..., c0:c1])
+            return out
+    _launch(family, dev, dtype, family.scalars(m, n, k, flag, rcond), a, b, out)
     return out
 
 
@@ -154,71 +158,8 @@ def _svd_ok(a):
     return 0 < a.shape[-1] <= SVD_MAX_DIM and 0 < a.shape[-2] <= SVD_MAX_DIM
 
 
-def _svd_solve(a, b, flag, rcond, out=None):
-    """X = a^+ b on the kernel: a (..., m, n), m, n <= 8; b (..., m, k) or None (identity, k = m); forward only.
-    Column blocks as in `_solve`."""
-    dev, dtype = a.device, a.dtype
-    m, n = a.shape[-2:]
-    k = m if b is None else b.shape[-1]
-    batch = a.shape[:-2] if b is None else broadcast_shapes(a.shape[:-2], b.shape[:-2])
-    shape = tuple(batch) + (n, k)
-    if out is None:
-        out = _like(b, shape, dtype, dev)
-    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev:
-        raise ValueError(f'out= must be a {dtype} tensor of shape {shape} on {dev}')
-    if out.numel() == 0:
-        return out
-    a = expand_batch(batch, a, 2)
-    if b is None:
-        _svd_launch(dev, dtype, m, n, m, flag, rcond, a, None, out)
-        return out
-    b = expand_batch(batch, b, 2)
-    cap = svd_max_cols(dtype, m, n)
-    for c0 in range(0, k, cap):
-        c1 = min(c0 + cap, k)
-        if c0 == 0 and c1 == k:
-            _svd_launch(dev, dtype, m, n, k, flag, rcond, a, b, out)
-        else:
-            _svd_launch(dev, dtype, m, n, c1 - c0, flag, rcond, a, b[..., c0:c1], out[..., c0:c1])
-    return out
-
-
 def _lstsq_ok(a):
     return SVD_MAX_DIM < a.shape[-2] <= LSTSQ_MAX_ROWS and 0 < a.shape[-1] <= LSTSQ_MAX_N
-
-
-def _lstsq_launch(dev, dtype, m, n, k, rcond, a, b, out):
-    """one nfm_lstsq_solve call; a / b / out share their batch dims (views)"""
-    bt = Batch(out.shape[:-2], [a, b, out], [2, 2, 2])
-    o = bt.operands
-    call(_lib.lib().nfm_lstsq_solve, dev, dtype_code(dtype), m, n, k, float(rcond), bt.n_outer, bt.n_inner,
-         *_fields(o[0]), *_fields(o[1]), *_fields(o[2]))
-    bt.finish()
-
-
-def _lstsq_solve(a, b, rcond, out=None):
-    """X = pinv(a, rcond) b on the streaming kernel: a (..., m, n), 8 < m <= 4096, n <= 8; b (..., m, k); forward
-    only.  Column blocks as in `_solve`."""
-    dev, dtype = a.device, a.dtype
-    m, n = a.shape[-2:]
-    k = b.shape[-1]
-    batch = broadcast_shapes(a.shape[:-2], b.shape[:-2])
-    shape = tuple(batch) + (n, k)
-    if out is None:
-        out = _like(b, shape, dtype, dev)
-    elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev:
-        raise ValueError(f'out= must be a {dtype} tensor of shape {shape} on {dev}')
-    if out.numel() == 0:
-        return out
-    a, b = expand_batch(batch, a, 2), expand_batch(batch, b, 2)
-    cap = lstsq_max_cols(dtype, n)
-    for c0 in range(0, k, cap):
-        c1 = min(c0 + cap, k)
-        if c0 == 0 and c1 == k:
-            _lstsq_launch(dev, dtype, m, n, k, rcond, a, b, out)
-        else:
-            _lstsq_launch(dev, dtype, m, n, c1 - c0, rcond, a, b[..., c0:c1], out[..., c0:c1])
-    return out
 
 
 def _check_out(out, *tensors):
@@ -273,10 +214,10 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
         if needs_grad(a, b):
             return _torch_lmdiv(a, b, method, rcond, out)
         if method == 'pinv' and _lstsq_ok(a):
-            return _lstsq_solve(a, b, rcond, out)
+            return _kernel_solve(_LSTSQ, a, b, out, rcond=rcond)
         if not _svd_ok(a):
             return _torch_lmdiv(a, b, method, rcond, out)
-        return _svd_solve(a, b, _SVD_FLAGS[method], rcond, out)
+        return _kernel_solve(_SVD, a, b, out, _SVD_FLAGS[method], rcond)
     if a.shape[-1] > MAX_ORDER or a.shape[-1] == 0:
         return _torch_lmdiv(a, b, method, rcond, out)
     if needs_grad(a, b):
@@ -284,7 +225,7 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
             return _torch_lmdiv(a, b, method, rcond, None)
         from ._autograd import LmdivFn
         return LmdivFn.apply(a, b, _FLAGS[method])
-    return _solve(a, b, _FLAGS[method], out)
+    return _kernel_solve(_SQUARE, a, b, out, _FLAGS[method])
 
 
 def rmdiv(a, b, method='lu', rcond=1e-15, out=None):
@@ -320,11 +261,11 @@ def inv(a, method='lu', rcond=1e-15, out=None):
         return torch.linalg.inv(a, out=out)
     if method == 'chol':
         if 0 < n <= MAX_ORDER and not needs_grad(a):
-            return _solve(a, None, _lib.SOLVE_CHOL, out)
+            return _kernel_solve(_SQUARE, a, None, out, _lib.SOLVE_CHOL)
         eye = torch.eye(n, dtype=dtype, device=dev)
         return torch.cholesky_solve(eye, torch.linalg.cholesky(a, upper=False), upper=False, out=out)
     if _svd_ok(a) and not needs_grad(a):
-        return _svd_solve(a, None, _SVD_FLAGS[method], rcond, out)
+        return _kernel_solve(_SVD, a, None, out, _SVD_FLAGS[method], rcond)
     if method == 'svd':
         u, s, v = torch.svd(a)
         return give(v.matmul(u.transpose(-1, -2) / s[..., None]))

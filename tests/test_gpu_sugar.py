@@ -11,6 +11,7 @@ import pytest
 import torch
 from conftest import GOLDEN, TOL, relerr
 import _solver_ref as R
+import _lstsq_ref as Q
 
 pytestmark = pytest.mark.gpu
 DNS = ['f32', 'f64']
@@ -194,6 +195,73 @@ def test_layouts_read_in_place(dev, dn, N):
     assert x11.shape == (n, N, 11) and x11.is_contiguous() and cap < 11
     for c0 in range(0, 11, cap):
         assert torch.equal(x11[..., c0:c0 + cap], s.lmdiv(ad, b11[..., c0:c0 + cap])), c0
+
+
+# ------------------------------------------------------------------------------------------------ column blocks
+# (family, method, rows, K per dtype): the smallest systems at which every family's column cap is below K
+BLOCK_CASES = [('lu', 'lu', 8, {'f64': 8, 'f32': 11}), ('chol', 'chol', 8, {'f64': 8, 'f32': 11}),
+               ('svd', 'svd', 8, {'f64': 8, 'f32': 11}), ('lstsq', 'pinv', 12, {'f64': 6, 'f32': 11})]
+
+
+def block_bound(family, a, got, b, dn, what):
+    """the family's per-record bound on one block of columns: `column_excess` against torch on the CPU in the
+    dtype (lu, chol, and the reference's svd composition), tests/_lstsq_ref.py's `excess` for the tall systems"""
+    if family == 'lstsq':
+        assert Q.excess(got, a, b, dn, what=what).max() <= 1.0, what
+        return
+    if family == 'svd':
+        u, sv, v = torch.svd(torch.from_numpy(np.array(a)))
+        ref = torch.matmul(v, u.transpose(-1, -2).matmul(torch.from_numpy(np.array(b))) / sv[..., None]).numpy()
+    else:
+        ref = cpu_ref(a, b, family)
+    column_excess(a, got, ref, b, a.shape[-1], dn, what)
+
+
+@pytest.mark.parametrize('dn', DNS)
+@pytest.mark.parametrize('case', BLOCK_CASES, ids=[case[0] for case in BLOCK_CASES])
+def test_column_blocks_are_the_separate_calls(dev, dn, case, monkeypatch):
+    """More columns than one launch takes, 130 records, every family: the result is bit for bit that of one call
+    per block of columns into the same view of a buffer of the same layout (the same kernel variant on both
+    sides), with a plain b, and with one broadcast a and out= a transposed view of a larger buffer; every block
+    meets the family's per-record bound."""
+    s = S()
+    family, method, M, ks = case
+    N, n, k = 8, 130, ks[dn]
+    cap = {'lu': lambda: s.max_cols(TT[dn], N), 'chol': lambda: s.max_cols(TT[dn], N),
+           'svd': lambda: s.svd_max_cols(TT[dn], M, N), 'lstsq': lambda: s.lstsq_max_cols(TT[dn], N)}[family]()
+    blocks = [(c0, min(c0 + cap, k)) for c0 in range(0, k, cap)]
+    assert 1 <= cap < k and len(blocks) == 2
+    rng = np.random.default_rng(300 + M)
+    g = rng.standard_normal((n, M, N))
+    if family == 'chol':
+        g = g @ g.transpose(0, 2, 1) + N * np.eye(N)
+    elif family != 'lstsq':
+        g = g + 6 * np.eye(N)
+    a = g.astype(R.NP[dn])
+    b = rng.standard_normal((n, M, k)).astype(R.NP[dn])
+    ad, bd = t(a, dev), t(b, dev)
+    launches = []
+    launch = s._launch
+    monkeypatch.setattr(s, '_launch', lambda *args: (launches.append(args[-1].shape[-1]), launch(*args))[1])
+
+    def check(a_np, a_dev, got, full, what):
+        assert launches == [c1 - c0 for c0, c1 in blocks], (what, launches)
+        assert full.stride() == got.stride() and got.shape == (n, N, k)
+        for c0, c1 in blocks:
+            assert s.lmdiv(a_dev, bd[..., c0:c1], method=method, out=full[..., c0:c1]).shape == (n, N, c1 - c0)
+        assert torch.equal(got, full), what
+        for c0, c1 in blocks:
+            block_bound(family, a_np, c(got)[..., c0:c1], b[..., c0:c1], dn, f'{what} {family} {dn} columns {c0}:{c1}')
+
+    got = s.lmdiv(ad, bd, method=method)
+    assert got.is_contiguous()
+    check(a, ad, got, torch.empty_like(got), 'plain b')
+    # one a for every b, the result into a transposed view of a larger buffer
+    del launches[:]
+    view = (lambda: torch.zeros(n + 3, k + 2, N + 1, dtype=TT[dn], device=dev)[:n, :k, :N].transpose(-1, -2))
+    out = view()
+    assert s.lmdiv(ad[:1], bd, method=method, out=out) is out and not out.is_contiguous()
+    check(np.broadcast_to(a[:1], a.shape), ad[:1], out, view(), 'broadcast a, out= a transposed view')
 
 
 @pytest.mark.parametrize('dn', DNS)

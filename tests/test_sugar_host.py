@@ -90,6 +90,35 @@ def test_cpu_tensors_are_refused():
     assert S._method('lu', b) == 'pinv'                     # non-square: always the pseudo-inverse
 
 
+def test_column_blocks_of_the_shared_solve_path(L, monkeypatch):
+    """the split of k columns at `cap` per launch; with the launch helper counted (nothing runs: CPU tensors never
+    reach a kernel), a k that fits is one launch on a, b and out themselves, a wider one a launch per block on views"""
+    from nitorch_fastmath_amd import sugar as S
+    assert S._blocks(8, 8) == [(0, 8)] and S._blocks(8, 6) == [(0, 6), (6, 8)] and S._blocks(1, 4) == [(0, 1)]
+    assert S._blocks(11, 8) == [(0, 8), (8, 11)] and S._blocks(12, 4) == [(0, 4), (4, 8), (8, 12)]
+    seen = []
+    monkeypatch.setattr(S, '_launch', lambda family, dev, dtype, scalars, a, b, out: seen.append((scalars, a, b, out)))
+    a, a12 = torch.zeros(5, 8, 8, dtype=torch.float64), torch.zeros(5, 12, 8, dtype=torch.float64)
+    for family, sys_, flag, cap in ((S._SQUARE, a, LU, S.max_cols(a.dtype, 8)), (S._SVD, a, 1, S.svd_max_cols(a.dtype, 8, 8)),
+                                    (S._LSTSQ, a12, None, S.lstsq_max_cols(a.dtype, 8))):
+        m = sys_.shape[-2]
+        head = (lambda k: {S._SQUARE: (8, k, flag), S._SVD: (8, 8, k, flag, 0.5), S._LSTSQ: (12, 8, k, 0.5)}[family])
+        b, out = torch.zeros(5, m, cap, dtype=a.dtype), torch.zeros(5, 8, cap, dtype=a.dtype)
+        del seen[:]
+        assert S._kernel_solve(family, sys_, b, out, flag, 0.5) is out and len(seen) == 1
+        assert seen[0][0] == head(cap) and seen[0][1] is sys_ and seen[0][2] is b and seen[0][3] is out
+        b, out = torch.zeros(5, m, cap + 2, dtype=a.dtype), torch.zeros(5, 8, cap + 2, dtype=a.dtype)
+        del seen[:]
+        S._kernel_solve(family, sys_, b, out, flag, 0.5)
+        assert [(sc, tuple(x.shape), x.data_ptr() - out.data_ptr()) for sc, _, _, x in seen] == \
+            [(head(cap), (5, 8, cap), 0), (head(2), (5, 8, 2), cap * 8)]
+        assert [tuple(x.shape) for _, _, x, _ in seen] == [(5, m, cap), (5, m, 2)]
+    del seen[:]                                           # the identity: one launch, k = n (lu, chol) or m (svd)
+    assert S._kernel_solve(S._SQUARE, a, None, None, CHOL).shape == (5, 8, 8) and seen[0][0] == (8, 8, CHOL)
+    assert S._kernel_solve(S._SVD, a12[:, :8, :3], None, None, 0, 0.5).shape == (5, 3, 8) and seen[1][0] == (8, 3, 8, 0, 0.5)
+    assert len(seen) == 2 and seen[0][2] is None and seen[1][2] is None
+
+
 # ------------------------------------------------------------------------------------------------ the C ABI
 def solve(L, dtype=F32, N=3, K=3, flags=LU, no=1, ni=1, a=4096, b=4096, out=4096):
     st = (0, 1, 1, 1)
