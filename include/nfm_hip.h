@@ -456,6 +456,26 @@ int nfm_sugar_solve(int dtype, int N, int K, int flags, int64_t n_outer, int64_t
  * NFM_ESIZE for an unknown dtype / an order outside 1..NFM_SOLVE_MAX_DIM */
 int nfm_sugar_max_cols(int dtype, int N);
 
+/* The same solve for the square orders NFM_ROWSOLVE_MIN_DIM..NFM_MAX_DIM (9..16), one row of [A | B] per lane slot
+ * (16 / R lanes per matrix): the arguments, the flags, the identity for b == NULL (K == N; NFM_SOLVE_LU then runs
+ * nfm_batch_inv, NFM_SOLVE_CHOL one launch per block of columns), the layouts read in place and `out` aliasing `b`
+ * are those of nfm_sugar_solve.  NFM_SOLVE_LU pivots on the first row with the largest |a_rk| (compared at 20
+ * mantissa bits in float64); NFM_SOLVE_CHOL eliminates without exchanges on the matrix rebuilt from the LOWER
+ * triangle and gives NaN in every entry of a record with a pivot that is not positive.  Column j of X has the same
+ * bits whatever K it was solved with and whatever the layout.  K in 1..nfm_rowsolve_max_cols(dtype, N) with a b.
+ * Status precedence: NFM_EDTYPE; NFM_EINVAL negative count; NFM_ESIZE n_outer; NFM_ESIZE N outside 9..16 or K
+ * outside 1..16; NFM_EINVAL unknown flag, or b == NULL with K != N; NFM_ESIZE K above the cap; then a, b, out in
+ * this order: NFM_EINVAL for a null pointer with a non-empty batch, NFM_EALIGN.  An empty batch with null pointers
+ * succeeds without a launch. */
+#define NFM_ROWSOLVE_MIN_DIM 9
+int nfm_rowsolve(int dtype, int N, int K, int flags, int64_t n_outer, int64_t n_inner,
+                 const void *a, int64_t a_so, int64_t a_si, int64_t a_sr, int64_t a_sc,
+                 const void *b, int64_t b_so, int64_t b_si, int64_t b_sr, int64_t b_sc,
+                 void *out, int64_t o_so, int64_t o_si, int64_t o_sr, int64_t o_sc, void *stream);
+/* largest K one nfm_rowsolve call takes at order N; NFM_EDTYPE / NFM_ESIZE for an unknown dtype / an order outside
+ * NFM_ROWSOLVE_MIN_DIM..NFM_MAX_DIM */
+int nfm_rowsolve_max_cols(int dtype, int N);
+
 /* X = A^+ B for one M x N matrix and one M x K matrix of right-hand sides per batch element, by a one-sided Jacobi
  * SVD held in the lane's registers: `lmdiv` / `rmdiv` / `solvevec` / `inv` of the reference's `sugar.py` with
  * method 'svd' or 'pinv', and its non-square systems (least squares for M > N, minimum norm for M < N).  X is

@@ -261,13 +261,14 @@ class BatchInvFn(torch.autograd.Function):
 
 class LmdivFn(torch.autograd.Function):
     """X = A^-1 B (sugar.lmdiv on the kernel):  dB = A^-T G, the same kernel with a's row and column strides
-    swapped;  dA = -dB X^T.  `flag` SOLVE_CHOL is only reached with a constant (symmetric) A: dB = A^-1 G."""
+    swapped;  dA = -dB X^T.  `flag` SOLVE_CHOL is only reached with a constant (symmetric) A: dB = A^-1 G.
+    The kernel family goes by the order: the lane-per-system kernels up to 8, the row-per-lane kernels at 9..16."""
 
     @staticmethod
     def forward(ctx, a, b, flag):
         from . import sugar as S
         with torch.no_grad():
-            x = S._kernel_solve(S._SQUARE, a, b, flag=flag)
+            x = S._kernel_solve(S._square_family(a.shape[-1]), a, b, flag=flag)
         ctx.flag = flag
         ctx.save_for_backward(a, x)
         ctx.shapes = (a.shape, b.shape)
@@ -278,7 +279,8 @@ class LmdivFn(torch.autograd.Function):
     def backward(ctx, g):
         from . import sugar as S
         a, x = ctx.saved_tensors
-        gb = S._kernel_solve(S._SQUARE, a if ctx.flag == _lib.SOLVE_CHOL else a.transpose(-1, -2), g, flag=ctx.flag)
+        gb = S._kernel_solve(S._square_family(a.shape[-1]), a if ctx.flag == _lib.SOLVE_CHOL else a.transpose(-1, -2), g,
+                             flag=ctx.flag)
         ga = None
         if ctx.needs_input_grad[0]:
             ga = _sum_to(-_small_matmul(gb, x.transpose(-1, -2)), ctx.shapes[0])

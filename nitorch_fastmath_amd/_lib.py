@@ -25,6 +25,7 @@ SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
 SP_BESSELI, SP_BESSELI_BWD, SP_RATIO, SP_RATIO_BWD, SP_MVDIGAMMA, SP_MVDIGAMMA_BWD = range(6)
 SP_MAX_N = 8
 SOLVE_LU, SOLVE_CHOL, SOLVE_MAX_DIM = 0, 1, 8    # include/nfm_hip.h: NFM_SOLVE_*
+ROWSOLVE_MIN_DIM = 9                             # include/nfm_hip.h: NFM_ROWSOLVE_MIN_DIM; nfm_rowsolve serves 9..MAX_DIM
 SVD_PLAIN, SVD_PINV, SVD_MAX_DIM, SVD_MAX_SWEEPS = 0, 1, 8, 16    # include/nfm_hip.h: NFM_SVD_*
 LSTSQ_MAX_ROWS, LSTSQ_MAX_N = 4096, 8    # include/nfm_hip.h: NFM_LSTSQ_MAX_ROWS, the N of nfm_lstsq_solve
 # include/nfm_hip.h: NFM_RT_*
@@ -75,6 +76,8 @@ SIGNATURES = {
     'nfm_special_host_eval': [_i, _i, _i, ctypes.c_double, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_sugar_solve': [_i, _i, _i, _i, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
     'nfm_sugar_max_cols': [_i, _i],
+    'nfm_rowsolve': [_i, _i, _i, _i, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
+    'nfm_rowsolve_max_cols': [_i, _i],
     'nfm_svd_solve': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64] + [_vp],
     'nfm_svd_solve_host': [_i, _i, _i, _i, _i, ctypes.c_double, _i64, _i64] + 3 * [_vp, _i64, _i64, _i64, _i64],
     'nfm_svd_max_cols': [_i, _i, _i],

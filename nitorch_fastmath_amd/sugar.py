@@ -7,9 +7,12 @@ kernel: `nfm_sugar_solve` for `lu` / `chol` on square matrices (Gaussian elimina
 system (one-sided Jacobi SVD on the rows of `[A | B]`: least squares for m > n, minimum norm for m < n).  Tall
 least-squares systems -- more than 8 rows (up to 4096), at most 8 columns: a model fit per voxel -- run
 `nfm_lstsq_solve`: the rows of `[A | B]` stream once past an n x n triangle in the lane's registers (Givens
-rotations) and the same Jacobi routine finishes on it, `pinv(a, rcond) @ b` in one launch.  The
+rotations) and the same Jacobi routine finishes on it, `pinv(a, rcond) @ b` in one launch.  Square
+systems of order 9..16 with `lu` / `chol` run `nfm_rowsolve`: the rows of `[A | B]` spread over the lanes of a
+matrix, Gauss-Jordan with partial pivoting (`lu`) or without exchanges on the lower triangle (`chol`).  The
 reference runs torch's batched LU / SVD, which are slow on tiny matrices.  Transposed, broadcast, padded and
-channel-first operands are read in place.  More than 8 columns, square orders above 8, `inv` of a tall matrix,
+channel-first operands are read in place.  Non-square systems of more than 8 columns, square orders above 16,
+`inv` of a tall matrix,
 and `svd` / `pinv` / non-square calls that need a gradient, take
 the reference's own torch composition on the device; the remaining names (`kron2`, `outer`, `trace`, `dot`,
 `mdot`, `is_orthonormal`, `round`) are torch compositions on the device, without a kernel.
@@ -57,6 +60,9 @@ _SVD = _Family('nfm_svd_solve', lambda m, n, k, flag, rcond: (m, n, k, flag, flo
                'nfm_svd_max_cols', lambda m, n: (m, n), -2)
 _LSTSQ = _Family('nfm_lstsq_solve', lambda m, n, k, flag, rcond: (m, n, k, float(rcond)),
                  'nfm_lstsq_max_cols', lambda m, n: (n,), None)
+_ROWSOLVE = _Family('nfm_rowsolve', lambda m, n, k, flag, rcond: (n, k, flag),
+                    'nfm_rowsolve_max_cols', lambda m, n: (n,), -1)
+ROWSOLVE_ORDERS = range(_lib.ROWSOLVE_MIN_DIM, _lib.MAX_DIM + 1)
 _caps = {}
 
 
@@ -71,6 +77,18 @@ def _cap(query, dtype, *dims):
 def max_cols(dtype, n):
     """Columns of `b` one launch takes at order `n` (the library's table, `nfm_sugar_max_cols`)."""
     return _cap(_SQUARE.cap, dtype, n)
+
+
+def rowsolve_max_cols(dtype, n):
+    """Columns of `b` one launch takes at an order `n` in 9..16 (the library's answer, `nfm_rowsolve_max_cols`)."""
+    return _cap(_ROWSOLVE.cap, dtype, n)
+
+
+def _square_family(n):
+    """the kernel family of a square `lu` / `chol` system of order n, None beyond the kernels"""
+    if 0 < n <= MAX_ORDER:
+        return _SQUARE
+    return _ROWSOLVE if n in ROWSOLVE_ORDERS else None
 
 
 def svd_max_cols(dtype, m, n):
@@ -198,6 +216,10 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
     method : `{'lu', 'chol', 'svd', 'pinv'}`; non-square `a` always takes `pinv`.
     `a` with m, n <= 8 runs a HIP kernel: elimination (`lu`), Cholesky from the lower triangle only (`chol`), or
     the Jacobi SVD (`svd`, `pinv`, every non-square `a`; forward only -- with a gradient: the torch composition).
+    A square `a` of order 9..16 with `lu` / `chol` runs the row-per-lane kernel (`nfm_rowsolve`): the same
+    contract -- lower triangle only and NaN records for `chol`, inf / NaN in a singular record for `lu`, every
+    layout read in place, differentiable with `lu` -- and a column of the result does not depend on how many
+    columns `b` has.  Order 17 and above take the torch composition.
     `pinv` drops the singular values `<= rcond sigma_max`; `svd` divides by every one of them.
     A tall `a` with 8 < m <= 4096 rows and n <= 8 columns runs the streaming least-squares kernel
     (`nfm_lstsq_solve`; forward only): exactly `pinv(a, rcond) @ b`, the minimum-norm least-squares solution.
@@ -218,14 +240,15 @@ def lmdiv(a, b, method='lu', rcond=1e-15, out=None):
         if not _svd_ok(a):
             return _torch_lmdiv(a, b, method, rcond, out)
         return _kernel_solve(_SVD, a, b, out, _SVD_FLAGS[method], rcond)
-    if a.shape[-1] > MAX_ORDER or a.shape[-1] == 0:
+    family = _square_family(a.shape[-1])
+    if family is None:
         return _torch_lmdiv(a, b, method, rcond, out)
     if needs_grad(a, b):
         if method == 'chol' and a.requires_grad:     # differentiates through the lower triangle only, like torch
             return _torch_lmdiv(a, b, method, rcond, None)
         from ._autograd import LmdivFn
         return LmdivFn.apply(a, b, _FLAGS[method])
-    return _kernel_solve(_SQUARE, a, b, out, _FLAGS[method])
+    return _kernel_solve(family, a, b, out, _FLAGS[method])
 
 
 def rmdiv(a, b, method='lu', rcond=1e-15, out=None):
@@ -242,7 +265,7 @@ def rmdiv(a, b, method='lu', rcond=1e-15, out=None):
 
 def inv(a, method='lu', rcond=1e-15, out=None):
     """Matrix inversion (sugar.py:194-258).  `lu`: `batchinv` up to order 16; `chol`: the kernel of `lmdiv`
-    against an identity generated in registers (order <= 8), for every batch rank; `svd` / `pinv` and every
+    against an identity generated in registers (order <= 16; 9..16 on the row-per-lane kernel), for every batch rank; `svd` / `pinv` and every
     non-square `a` (m, n <= 8): the Jacobi SVD kernel against the identity, `(..., n, m)`."""
     dev, dtype, (a,) = prepare(None, a, grad_ok=True)
     _check_out(out, a)
@@ -260,8 +283,9 @@ def inv(a, method='lu', rcond=1e-15, out=None):
             return give(batchinv(a))
         return torch.linalg.inv(a, out=out)
     if method == 'chol':
-        if 0 < n <= MAX_ORDER and not needs_grad(a):
-            return _kernel_solve(_SQUARE, a, None, out, _lib.SOLVE_CHOL)
+        family = _square_family(n)
+        if family is not None and not needs_grad(a):
+            return _kernel_solve(family, a, None, out, _lib.SOLVE_CHOL)
         eye = torch.eye(n, dtype=dtype, device=dev)
         return torch.cholesky_solve(eye, torch.linalg.cholesky(a, upper=False), upper=False, out=out)
     if _svd_ok(a) and not needs_grad(a):
