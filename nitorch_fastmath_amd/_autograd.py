@@ -385,7 +385,9 @@ class PickFn(torch.autograd.Function):
             else:
                 val, idx = fn(input, dim=dim, keepdim=True, omitnan=omitnan, return_indices=True)
                 ctx.cfg = (dim, keepdim, tuple(input.shape))
-        ctx.save_for_backward(idx)
+        # nanmax / nanmin: a NaN gets no gradient, not even where an all-NaN slice returns position 0
+        ctx.omitnan = bool(omitnan)
+        ctx.save_for_backward(idx, *([input] if omitnan else []))
         ctx.in_dtype = input.dtype
         if dim is None:
             return val.reshape([1] * input.dim()) if keepdim else val
@@ -400,13 +402,19 @@ class PickFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         from .utils import ensure_list
-        (idx,) = ctx.saved_tensors
+        idx = ctx.saved_tensors[0]
         dim, keepdim, shape = ctx.cfg
+
+        def deliver(out):
+            if ctx.omitnan:
+                out = torch.where(torch.isnan(ctx.saved_tensors[1]), torch.zeros_like(out), out)
+            return out.to(ctx.in_dtype), None, None, None, None
+
         nd = len(shape)
         if dim is None:
             out = torch.zeros(shape, dtype=g.dtype, device=g.device)
             out.view(-1)[idx] = g.reshape(())
-            return out.to(ctx.in_dtype), None, None, None, None
+            return deliver(out)
         dims = [d if d >= 0 else nd + d for d in ensure_list(dim)]
         g = g if keepdim else _unsq(g, nd, dims, False)
         scalar = not isinstance(dim, (list, tuple, range))
@@ -416,7 +424,7 @@ class PickFn(torch.autograd.Function):
                                indexing='ij')
         index = [sub[..., dims.index(d)] if d in dims else grids[d] for d in range(nd)]
         out.index_put_(tuple(index), g.expand(sub.shape[:-1]), accumulate=True)
-        return out.to(ctx.in_dtype), None, None, None, None
+        return deliver(out)
 
 
 class VarFn(torch.autograd.Function):
@@ -464,7 +472,8 @@ class VarFn(torch.autograd.Function):
         den = n - (1 if unbiased else 0)
         gx = 2.0 * (x.to(torch.float64) - mean) / den
         if std:
-            gx = gx / (2.0 * out)
+            # a slice without spread (std == 0) gets no gradient, as in torch.std's backward pass
+            gx = torch.where(out == 0, torch.zeros_like(gx), gx / (2.0 * out))
         gx = gx * g
         if omitnan:
             gx = torch.where(torch.isnan(x), torch.zeros_like(gx), gx)

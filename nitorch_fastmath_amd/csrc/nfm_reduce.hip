@@ -91,14 +91,50 @@ __global__ __launch_bounds__(kRedThreads) void reduce_all_k2(const double *__res
     }
 }
 
+// moments of the whole array: the streaming structure of reduce_all_k1 with one MomCore per load in
+// flight; a workgroup leaves [n, s, q, K] and the second kernel merges the workgroups' records
+template <typename T>
+__device__ __forceinline__ MomCore<T> mom_block(MomCore<T> t, MomCore<T> *lds)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t.merge(t.shfl(off));
+    if (threadIdx.x % kWave == 0) lds[threadIdx.x / kWave] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t = lds[0];
+        for (int w = 1; w < kRedThreads / kWave; ++w) t.merge(lds[w]);
+    }
+    return t; // valid in thread 0
+}
+
+// fold one vector / one element; `unset`: the accumulator has seen no finite value yet and looks for
+// its shift in what it is about to fold (MomCore::seed)
+template <typename T>
+__device__ __forceinline__ void fold_vec(MomCore<T> &m, bool &unset, typename VecOf<T>::type v)
+{
+    constexpr int VEC = VecOf<T>::N;
+    T c[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) c[k] = v[k];
+    if (unset) unset = m.seed(c);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) m.fold(c[k]);
+}
+template <typename T>
+__device__ __forceinline__ void fold_one(MomCore<T> &m, bool &unset, T v)
+{
+    const T c[1] = {v};
+    if (unset) unset = m.seed(c);
+    m.fold(v);
+}
+
 template <typename T>
 __global__ __launch_bounds__(kRedThreads) void moments_all_k1(const T *__restrict__ x, int64_t n,
                                                                double *__restrict__ partial)
 {
     using V = typename VecOf<T>::type;
     constexpr int VEC = VecOf<T>::N;
-    __shared__ Mom lds[kRedThreads / kWave];
-    const double shift = pick_shift(x, n, 1);
+    __shared__ MomCore<T> lds[kRedThreads / kWave];
     // same streaming structure as reduce_all_k1: unaligned head, 16-byte vectors, tail
     const uintptr_t addr = reinterpret_cast<uintptr_t>(x);
     int64_t head = ((16 - (addr & 15)) & 15) / (int64_t)sizeof(T);
@@ -106,7 +142,10 @@ __global__ __launch_bounds__(kRedThreads) void moments_all_k1(const T *__restric
     const int64_t nvec = (n - head) / VEC;
     const int64_t tail0 = head + nvec * VEC;
     const V *xv = reinterpret_cast<const V *>(x + head);
-    Mom m = {0.0, 0.0, 0.0}, m1 = m, m2 = m, m3 = m;
+    MomCore<T> m, m1, m2, m3;
+    m.init(x, n, 1);
+    m1 = m2 = m3 = m;
+    bool u = m.unset(), u1 = u, u2 = u, u3 = u;
     const int64_t stride = (int64_t)gridDim.x * kRedThreads;
     int64_t q = (int64_t)blockIdx.x * kRedThreads + threadIdx.x;
     for (; q + 3 * stride < nvec; q += 4 * stride) {
@@ -114,54 +153,36 @@ __global__ __launch_bounds__(kRedThreads) void moments_all_k1(const T *__restric
         const V v1 = __builtin_nontemporal_load(xv + q + stride);
         const V v2 = __builtin_nontemporal_load(xv + q + 2 * stride);
         const V v3 = __builtin_nontemporal_load(xv + q + 3 * stride);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) {
-            mom_fold(m, v0[k], shift);
-            mom_fold(m1, v1[k], shift);
-            mom_fold(m2, v2[k], shift);
-            mom_fold(m3, v3[k], shift);
-        }
+        fold_vec(m, u, v0);
+        fold_vec(m1, u1, v1);
+        fold_vec(m2, u2, v2);
+        fold_vec(m3, u3, v3);
     }
-    for (; q < nvec; q += stride) {
-        const V v0 = xv[q];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) mom_fold(m, v0[k], shift);
-    }
+    for (; q < nvec; q += stride) fold_vec(m, u, xv[q]);
     const int64_t gid = (int64_t)blockIdx.x * kRedThreads + threadIdx.x;
-    if (gid < head) mom_fold(m1, x[gid], shift);
-    if (gid < n - tail0) mom_fold(m2, x[tail0 + gid], shift);
-    m = mom_merge(mom_merge(m, m1), mom_merge(m2, m3));
-    m = mom_wave(m);
-    if (threadIdx.x % kWave == 0) lds[threadIdx.x / kWave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Mom r = lds[0];
-        for (int w = 1; w < kRedThreads / kWave; ++w) r = mom_merge(r, lds[w]);
-        partial[3 * blockIdx.x + 0] = r.n;
-        partial[3 * blockIdx.x + 1] = r.s;
-        partial[3 * blockIdx.x + 2] = r.q;
-    }
+    if (gid < head) fold_one(m1, u1, x[gid]);
+    if (gid < n - tail0) fold_one(m2, u2, x[tail0 + gid]);
+    m.merge(m1);
+    m2.merge(m3);
+    m.merge(m2);
+    m = mom_block(m, lds);
+    if (threadIdx.x == 0) m.save(partial + 4 * blockIdx.x);
 }
 
 template <typename T>
 __global__ __launch_bounds__(kRedThreads) void moments_all_k2(const double *__restrict__ partial, int nparts,
-                                                               const T *__restrict__ x, int64_t n, double *out)
+                                                               double *out)
 {
-    __shared__ Mom lds[kRedThreads / kWave];
-    Mom m = {0.0, 0.0, 0.0};
-    for (int p = threadIdx.x; p < nparts; p += kRedThreads)
-        m = mom_merge(m, Mom{partial[3 * p], partial[3 * p + 1], partial[3 * p + 2]});
-    m = mom_wave(m);
-    if (threadIdx.x % kWave == 0) lds[threadIdx.x / kWave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Mom r = lds[0];
-        for (int w = 1; w < kRedThreads / kWave; ++w) r = mom_merge(r, lds[w]);
-        out[0] = r.n;
-        out[1] = r.s;
-        out[2] = r.q;
-        out[3] = pick_shift(x, n, 1);
+    __shared__ MomCore<T> lds[kRedThreads / kWave];
+    MomCore<T> m;
+    m.init_empty();
+    for (int p = threadIdx.x; p < nparts; p += kRedThreads) {
+        MomCore<T> u;
+        u.load(partial + 4 * p);
+        m.merge(u);
     }
+    m = mom_block(m, lds);
+    if (threadIdx.x == 0) m.save(out);
 }
 
 template <typename T, int OP>
@@ -181,13 +202,11 @@ int moments_all_launch(int dtype, const void *x, int64_t n, void *workspace, dou
     if (dtype == NFM_F32) {
         hipLaunchKernelGGL((moments_all_k1<float>), dim3(kRedBlocks), dim3(kRedThreads), 0, s,
                            static_cast<const float *>(x), n, partial);
-        hipLaunchKernelGGL((moments_all_k2<float>), dim3(1), dim3(kRedThreads), 0, s, partial, kRedBlocks,
-                           static_cast<const float *>(x), n, out);
+        hipLaunchKernelGGL((moments_all_k2<float>), dim3(1), dim3(kRedThreads), 0, s, partial, kRedBlocks, out);
     } else {
         hipLaunchKernelGGL((moments_all_k1<double>), dim3(kRedBlocks), dim3(kRedThreads), 0, s,
                            static_cast<const double *>(x), n, partial);
-        hipLaunchKernelGGL((moments_all_k2<double>), dim3(1), dim3(kRedThreads), 0, s, partial, kRedBlocks,
-                           static_cast<const double *>(x), n, out);
+        hipLaunchKernelGGL((moments_all_k2<double>), dim3(1), dim3(kRedThreads), 0, s, partial, kRedBlocks, out);
     }
     return launch_status();
 }
@@ -198,7 +217,7 @@ using namespace nfm;
 
 extern "C" {
 
-size_t nfm_reduce_workspace_bytes(void) { return (size_t)kRedBlocks * 3 * sizeof(double); }
+size_t nfm_reduce_workspace_bytes(void) { return (size_t)kRedBlocks * 4 * sizeof(double); } // moments: [n, s, q, K] per workgroup
 
 int nfm_reduce_all(int dtype, int op, int out_dtype, int64_t n, const void *x, void *workspace,
                    size_t workspace_bytes, void *out, void *stream)

@@ -74,13 +74,12 @@ struct Pick {
 };
 
 // ---- one-pass moments: [count, sum(x - K), sum((x - K)^2), K] over the non-NaN elements,
-// K = the first finite element (a shift that removes the cancellation of the raw-moment
-// variance formula).  Feeds nanmean / nanvar / nanstd (reduce.py:553-763) in ONE pass over
-// memory instead of three.
+// K = a finite element of the slice (a shift that removes the cancellation of the raw-moment
+// variance formula: |x - K| <= max - min whichever element it is).  Feeds nanmean / nanvar /
+// nanstd (reduce.py:553-763) in ONE pass over memory instead of three.
 struct Mom {
     double n, s, q;
 };
-__device__ __forceinline__ Mom mom_merge(Mom a, Mom b) { return {a.n + b.n, a.s + b.s, a.q + b.q}; }
 template <typename T>
 __device__ __forceinline__ void mom_fold(Mom &m, T v, double shift)
 {
@@ -90,20 +89,11 @@ __device__ __forceinline__ void mom_fold(Mom &m, T v, double shift)
     m.s += d;
     m.q += d * d;
 }
-__device__ __forceinline__ Mom mom_wave(Mom m)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m.n += __shfl_xor(m.n, off, kWave);
-        m.s += __shfl_xor(m.s, off, kWave);
-        m.q += __shfl_xor(m.q, off, kWave);
-    }
-    return m;
-}
 template <typename T>
 __device__ __forceinline__ double pick_shift(const T *x, int64_t n, int64_t stride)
 {
-    // first finite value among the first few elements (uniform across the block)
+    // first finite value among the first few elements (uniform across the accumulators of a slice,
+    // so that their merges need no re-centring); 0 = none found, the accumulator picks its own
     double k = 0.0;
     for (int64_t j = 0; j < n && j < 8; ++j) {
         const double v = (double)x[j * stride];
@@ -111,6 +101,76 @@ __device__ __forceinline__ double pick_shift(const T *x, int64_t n, int64_t stri
     }
     return k;
 }
+// A moment accumulator and its shift.  The shift is never left at 0 by default: an accumulator that
+// has seen no finite value yet (unset(): a slice that starts with NaNs, a lane whose first vectors
+// are all NaN) takes the first finite value of the next batch it folds (seed()).  The kernels keep
+// one bit per accumulator for this and test the bits once per batch of loads, not per element, so
+// the steady state stays load-bound.  Accumulators of one slice may therefore differ in their
+// shifts; merge() re-centres in double.
+template <typename T>
+struct MomCore {
+    Mom m;
+    double k;
+    __device__ __forceinline__ void init_empty()
+    {
+        m = {0.0, 0.0, 0.0};
+        k = 0.0;
+    }
+    __device__ __forceinline__ void init(const T *p0, int64_t cnt, int64_t stride)
+    {
+        m = {0.0, 0.0, 0.0};
+        k = pick_shift(p0, cnt, stride);
+    }
+    // no shift and nothing counted: the next batch may seed
+    __device__ __forceinline__ bool unset() const { return k == 0.0 && m.n == 0.0; }
+    // shift = the first finite value of the batch about to be folded; true if it holds none
+    template <int N>
+    __device__ __forceinline__ bool seed(const T (&v)[N])
+    {
+        bool none = true;
+#pragma unroll
+        for (int j = N - 1; j >= 0; --j) {
+            const double d = (double)v[j];
+            const bool fin = d - d == 0.0;
+            k = fin ? d : k;
+            none = none && !fin;
+        }
+        return none;
+    }
+    __device__ __forceinline__ void fold(T v) { mom_fold(m, v, k); }
+    // the two sides may use different shifts: re-centre the other side's sums on ours
+    // (sum(x - K1) = sum(x - K2) + n (K2 - K1), likewise for the squares)
+    __device__ __forceinline__ void merge(const MomCore &o)
+    {
+        const double kk = (m.n == 0.0) ? o.k : k;
+        const double d = o.k - kk;
+        m.s += o.m.s + o.m.n * d;
+        m.q += o.m.q + (2.0 * d) * o.m.s + o.m.n * d * d;
+        m.n += o.m.n;
+        k = kk;
+    }
+    __device__ __forceinline__ MomCore shfl(int off) const
+    {
+        MomCore o;
+        o.m.n = __shfl_xor(m.n, off, kWave);
+        o.m.s = __shfl_xor(m.s, off, kWave);
+        o.m.q = __shfl_xor(m.q, off, kWave);
+        o.k = __shfl_xor(k, off, kWave);
+        return o;
+    }
+    __device__ __forceinline__ void save(double *p) const
+    {
+        p[0] = m.n;
+        p[1] = m.s;
+        p[2] = m.q;
+        p[3] = k;
+    }
+    __device__ __forceinline__ void load(const double *p)
+    {
+        m = {p[0], p[1], p[2]};
+        k = p[3];
+    }
+};
 
 #define NFM_SWITCH_OP(op, CALL)                         \
     switch (op) {                                       \

@@ -39,6 +39,7 @@ __device__ __forceinline__ void put_value(const FinParams &f, int64_t e, double 
 template <typename T, int OP>
 struct ValAcc {
     static constexpr int NP = 1;
+    static constexpr bool SEEDS = false; // no state to seed from the data (see MomAcc)
     double a;
     __device__ __forceinline__ void init_empty() { a = RedOp<OP>::identity(); }
     __device__ __forceinline__ void init(const T *, int64_t, int64_t) { init_empty(); }
@@ -61,6 +62,7 @@ struct ValAcc {
 template <typename T, int OP>
 struct PickAcc {
     static constexpr int NP = 2;
+    static constexpr bool SEEDS = false;
     T a;
     int64_t i; // -1: nothing seen yet
     __device__ __forceinline__ void init_empty()
@@ -113,73 +115,30 @@ struct PickAcc {
 };
 
 template <typename T>
-struct MomAcc {
+struct MomAcc : MomCore<T> {
     static constexpr int NP = 4;
-    Mom m;
-    double k;
-    __device__ __forceinline__ void init_empty()
-    {
-        m = {0.0, 0.0, 0.0};
-        k = 0.0;
-    }
-    __device__ __forceinline__ void init(const T *p0, int64_t cnt, int64_t stride)
-    {
-        m = {0.0, 0.0, 0.0};
-        k = pick_shift(p0, cnt, stride);
-    }
-    // shift = the first finite value among the lane's own elements (GROUP plan, inner == 1: no extra loads)
+    static constexpr bool SEEDS = true; // the shift may have to come from the values the lane folds
+    using MomCore<T>::m;
+    using MomCore<T>::k;
+    // shift = the first finite value among the lane's own elements (GROUP plan: no extra loads)
     template <int VEC>
     __device__ __forceinline__ void init_vals(const T (&v)[VEC], bool have)
     {
-        m = {0.0, 0.0, 0.0};
-        k = 0.0;
-        if (have) {
-#pragma unroll
-            for (int j = VEC - 1; j >= 0; --j) {
-                const double d = (double)v[j];
-                k = (d - d == 0.0) ? d : k;
-            }
-        }
+        this->init_empty();
+        if (have) this->seed(v);
     }
-    // shift = this accumulator's own first value (one element per lane and column)
     __device__ __forceinline__ void init_own(T v, bool have)
     {
-        m = {0.0, 0.0, 0.0};
-        const double d = (double)v;
-        k = (have && d - d == 0.0) ? d : 0.0;
+        const T one[1] = {v};
+        init_vals<1>(one, have);
     }
-    __device__ __forceinline__ void fold(T v, int64_t) { mom_fold(m, v, k); }
-    // the two sides may use different shifts: re-centre the other side's sums on ours
-    // (sum(x - K1) = sum(x - K2) + n (K2 - K1), likewise for the squares)
-    __device__ __forceinline__ void merge(const MomAcc &o)
-    {
-        const double kk = (m.n == 0.0) ? o.k : k;
-        const double d = o.k - kk;
-        m.s += o.m.s + o.m.n * d;
-        m.q += o.m.q + (2.0 * d) * o.m.s + o.m.n * d * d;
-        m.n += o.m.n;
-        k = kk;
-    }
+    __device__ __forceinline__ void fold(T v, int64_t) { MomCore<T>::fold(v); }
+    __device__ __forceinline__ void merge(const MomAcc &o) { MomCore<T>::merge(o); }
     __device__ __forceinline__ MomAcc shfl(int off) const
     {
         MomAcc o;
-        o.m.n = __shfl_xor(m.n, off, kWave);
-        o.m.s = __shfl_xor(m.s, off, kWave);
-        o.m.q = __shfl_xor(m.q, off, kWave);
-        o.k = __shfl_xor(k, off, kWave);
+        static_cast<MomCore<T> &>(o) = MomCore<T>::shfl(off);
         return o;
-    }
-    __device__ __forceinline__ void save(double *p) const
-    {
-        p[0] = m.n;
-        p[1] = m.s;
-        p[2] = m.q;
-        p[3] = k;
-    }
-    __device__ __forceinline__ void load(const double *p)
-    {
-        m = {p[0], p[1], p[2]};
-        k = p[3];
     }
     __device__ __forceinline__ void finish(const FinParams &f, int64_t e) const
     {
@@ -232,6 +191,51 @@ struct LoadV<double, 2> {
         v[0] = t[0], v[1] = t[1];
     }
 };
+
+// Seeding (accumulators with SEEDS, i.e. MomAcc): bit k of a lane's mask is set while accumulator k has
+// seen no finite value.  The loops test the mask once per batch of loads; while it is non-zero, the
+// accumulators concerned look for their shift in the values they are about to fold.  Component k of
+// every vector goes to accumulator k, except where a single accumulator folds whole vectors (ONE).
+template <class Acc, int NA>
+__device__ __forceinline__ unsigned unset_mask(const Acc (&acc)[NA])
+{
+    unsigned mask = 0;
+    if constexpr (Acc::SEEDS) {
+#pragma unroll
+        for (int k = 0; k < NA; ++k) mask |= acc[k].unset() ? 1u << k : 0u;
+    }
+    return mask;
+}
+template <class Acc, typename T, int VEC>
+__device__ __forceinline__ unsigned seed_cols(Acc (&acc)[VEC], unsigned mask, const T (&v0)[VEC], const T (&v1)[VEC],
+                                              const T (&v2)[VEC], const T (&v3)[VEC])
+{
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const T c[4] = {v0[k], v1[k], v2[k], v3[k]};
+        if ((mask >> k & 1u) && !acc[k].seed(c)) mask &= ~(1u << k);
+    }
+    return mask;
+}
+template <class Acc, typename T, int VEC>
+__device__ __forceinline__ unsigned seed_cols(Acc (&acc)[VEC], unsigned mask, const T (&v0)[VEC])
+{
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+        const T c[1] = {v0[k]};
+        if ((mask >> k & 1u) && !acc[k].seed(c)) mask &= ~(1u << k);
+    }
+    return mask;
+}
+template <class Acc, typename T, int VEC>
+__device__ __forceinline__ unsigned seed_one(Acc &acc, const T (&v0)[VEC], const T (&v1)[VEC], const T (&v2)[VEC],
+                                             const T (&v3)[VEC])
+{
+    T c[4 * VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) c[k] = v0[k], c[VEC + k] = v1[k], c[2 * VEC + k] = v2[k], c[3 * VEC + k] = v3[k];
+    return acc.seed(c) ? 1u : 0u;
+}
 
 // ---- GROUP: small slabs (red * inner elements, at most 4 KiB).  G = 2^lgG lanes share a slab:
 // lane `sub` of the group reads vectors sub, sub + G, ... of it (G * 16 B >= 128 B contiguous
@@ -341,14 +345,26 @@ __global__ __launch_bounds__(256) void reduce_group_k(const T *__restrict__ x, i
             }
         }
         if (valid) {
+            unsigned unset = 0; // accumulators still without a shift
+            if constexpr (Acc::SEEDS && !ONE) {
+                unset = unset_mask(acc);
+                if (unset) unset = seed_cols(acc, unset, v0);
+            }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) acc[ONE ? 0 : k].fold(v0[k], r0[k]);
+            if constexpr (Acc::SEEDS && ONE) unset = unset_mask(acc); // init_vals looked at v0
             int pos = pos0 + step, rr = rstep;
             for (; pos + 3 * step < L; pos += 4 * step, rr += 4 * rstep) {
                 LoadV<T, VEC>::ld(slab + pos, v0);
                 LoadV<T, VEC>::ld(slab + pos + step, v1);
                 LoadV<T, VEC>::ld(slab + pos + 2 * step, v2);
                 LoadV<T, VEC>::ld(slab + pos + 3 * step, v3);
+                if constexpr (Acc::SEEDS) {
+                    if (unset) {
+                        if constexpr (ONE) unset = seed_one(acc[0], v0, v1, v2, v3);
+                        else unset = seed_cols(acc, unset, v0, v1, v2, v3);
+                    }
+                }
                 if constexpr (ONE) { // keep the positions increasing inside the one accumulator
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) acc[0].fold(v0[k], r0[k] + rr);
@@ -370,6 +386,12 @@ __global__ __launch_bounds__(256) void reduce_group_k(const T *__restrict__ x, i
             }
             for (; pos < L; pos += step, rr += rstep) {
                 LoadV<T, VEC>::ld(slab + pos, v0);
+                if constexpr (Acc::SEEDS) {
+                    if (unset) {
+                        if constexpr (ONE) unset = acc[0].seed(v0) ? 1u : 0u;
+                        else unset = seed_cols(acc, unset, v0);
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) acc[ONE ? 0 : k].fold(v0[k], r0[k] + rr);
             }
@@ -414,6 +436,7 @@ __global__ __launch_bounds__(256) void reduce_flat_k(const T *__restrict__ x, in
         }
     }
     if (active) {
+        unsigned unset = unset_mask(acc); // accumulators still without a shift
         int64_t pos = start + (int64_t)lane * VEC;
         for (; pos + 3 * step + VEC <= end; pos += 4 * step) {
             T v0[VEC], v1[VEC], v2[VEC], v3[VEC];
@@ -421,6 +444,9 @@ __global__ __launch_bounds__(256) void reduce_flat_k(const T *__restrict__ x, in
             LoadV<T, VEC>::ld(slab + pos + step, v1);
             LoadV<T, VEC>::ld(slab + pos + 2 * step, v2);
             LoadV<T, VEC>::ld(slab + pos + 3 * step, v3);
+            if constexpr (Acc::SEEDS) {
+                if (unset) unset = seed_cols(acc, unset, v0, v1, v2, v3);
+            }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 acc[k].fold(v0[k], r[k]);
@@ -433,6 +459,9 @@ __global__ __launch_bounds__(256) void reduce_flat_k(const T *__restrict__ x, in
         for (; pos + VEC <= end; pos += step) {
             T v0[VEC];
             LoadV<T, VEC>::ld(slab + pos, v0);
+            if constexpr (Acc::SEEDS) {
+                if (unset) unset = seed_cols(acc, unset, v0);
+            }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 acc[k].fold(v0[k], r[k]);
@@ -441,8 +470,15 @@ __global__ __launch_bounds__(256) void reduce_flat_k(const T *__restrict__ x, in
         }
         if (VEC > 1 && pos < end) { // ragged end of the slab, shorter than one vector
 #pragma unroll
-            for (int k = 0; k < VEC; ++k)
-                if (pos + k < end) acc[k].fold(slab[pos + k], r[k]);
+            for (int k = 0; k < VEC; ++k) {
+                if (pos + k < end) {
+                    const T c[1] = {slab[pos + k]};
+                    if constexpr (Acc::SEEDS) {
+                        if (unset >> k & 1u) acc[k].seed(c);
+                    }
+                    acc[k].fold(c[0], r[k]);
+                }
+            }
         }
     }
 
@@ -550,6 +586,7 @@ __global__ __launch_bounds__(256) void reduce_col_k(const T *__restrict__ x, int
         if (red > 0) acc[k].init(p + k, red, inner);
         else acc[k].init_empty();
     }
+    unsigned unset = unset_mask(acc); // accumulators still without a shift
     int64_t r = r0;
     for (; r + 3 < r1; r += 4) {
         T v0[VEC], v1[VEC], v2[VEC], v3[VEC];
@@ -557,6 +594,9 @@ __global__ __launch_bounds__(256) void reduce_col_k(const T *__restrict__ x, int
         LoadV<T, VEC>::ld(p + (r + 1) * inner, v1);
         LoadV<T, VEC>::ld(p + (r + 2) * inner, v2);
         LoadV<T, VEC>::ld(p + (r + 3) * inner, v3);
+        if constexpr (Acc::SEEDS) {
+            if (unset) unset = seed_cols(acc, unset, v0, v1, v2, v3);
+        }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             acc[k].fold(v0[k], r);
@@ -568,6 +608,9 @@ __global__ __launch_bounds__(256) void reduce_col_k(const T *__restrict__ x, int
     for (; r < r1; ++r) {
         T v0[VEC];
         LoadV<T, VEC>::ld(p + r * inner, v0);
+        if constexpr (Acc::SEEDS) {
+            if (unset) unset = seed_cols(acc, unset, v0);
+        }
 #pragma unroll
         for (int k = 0; k < VEC; ++k) acc[k].fold(v0[k], r);
     }

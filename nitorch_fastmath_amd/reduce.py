@@ -404,17 +404,18 @@ def _stat_staged(kind, input, groups, keepdim, omitnan, unbiased, out_dtype):
     rest = [d for g in groups[:-1] for d in g]
     has = n > 0
     safe_n = torch.where(has, n, torch.ones_like(n))
-    mean_i = torch.where(has, k + s_ / safe_n, torch.zeros_like(n))
+    # like the kernels, the merge works on values relative to a shift taken from the data (per output
+    # entry: the largest shift of its slices), never on the raw magnitudes
+    k0 = torch.where(has, k, torch.full_like(k, -float('inf'))).amax(dim=rest, keepdim=True)
+    k0 = torch.where(torch.isfinite(k0), k0, torch.zeros_like(k0))           # nothing counted at all
+    rel_i = torch.where(has, (k - k0) + s_ / safe_n, torch.zeros_like(n))    # slice mean - k0
     m2_i = torch.where(has, q - s_ * s_ / safe_n, torch.zeros_like(n))
     cnt = n.sum(dim=rest)
-    mean = (n * mean_i).sum(dim=rest) / cnt
+    rel = (n * rel_i).sum(dim=rest, keepdim=True) / n.sum(dim=rest, keepdim=True)
     if kind == _STAT_MEAN:
-        v = mean
+        v = (k0 + rel).reshape(cnt.shape)
     else:
-        mexp = mean
-        for d in rest:
-            mexp = mexp.unsqueeze(d)
-        m2 = (m2_i + n * (mean_i - mexp) ** 2).sum(dim=rest)
+        m2 = (m2_i + n * (rel_i - rel) ** 2).sum(dim=rest)
         den = cnt - 1 if unbiased else cnt
         v = m2.clamp_min(0) / den
         v = torch.where(den > 0, v, torch.full_like(v, float('nan')))

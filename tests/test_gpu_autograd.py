@@ -328,3 +328,221 @@ def test_median_backward(dev):
     y = torch.randn(1000, device=dev, requires_grad=True)
     N_.reduce.median(y).backward()
     assert y.grad.sum() == 1 and y.grad[y.detach().argsort()[499]] == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Gradients of `reduce` on every route: float32 and float64 leaves, scalar / negative / adjacent / non-adjacent
+# (staged) / unsorted dims and the full reduction, keepdim both ways, dtype=, views, long reduced axes.
+# Expected gradients are the closed forms of tests/_reduce_ref.py in longdouble:
+#     sum   g on the counted elements (0 at omitted NaNs)      mean  g / n
+#     var   2 (x - mean) g / (n - ddof)                        std   var's gradient / (2 std)
+#     max, min, median   the whole cotangent at the returned index (first occurrence)
+# Bound per entry: eps |ref| (eps of the leaf's dtype) + the forward error propagated to first order,
+#     var   2 |g| / (n - ddof) . (eps64 |mean| + 2 n u R)
+#     std   that / (2 std) + |ref| (eps64 std + 8 n u R^2 n / ((n - ddof) 2 std)) / std
+# (the mean / variance terms of _reduce_ref.py, u = 2^-53, R = max - min of the slice).
+_GDT = {'f32': torch.float32, 'f64': torch.float64}
+_GRAD_DIMS = (1, -1, (1, 2), (0, 3), (2, 1), None)       # (0, 3): staged; (2, 1): unsorted
+
+
+def _leaf(x, dev, view=None):
+    """leaf on the device (and the tensor the function sees: the leaf itself or a view of it)"""
+    leaf = torch.from_numpy(np.ascontiguousarray(x)).to(dev).requires_grad_()
+    return leaf, (leaf if view is None else view(leaf))
+
+
+def _cotangent(out, rng, dev):
+    g = rng.standard_normal(tuple(out.shape))
+    gt = torch.from_numpy(g).to(out.dtype)
+    return gt.double().numpy(), gt.to(dev)
+
+
+def _grad_data(shape, dn, seed, nan_rate=0.05):
+    rng = np.random.default_rng(seed)
+    x = (3.0 + rng.standard_normal(shape)).astype(np.float32 if dn == 'f32' else np.float64)
+    if nan_rate:
+        x[rng.random(shape) < nan_rate] = np.nan
+    return x, rng
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+@pytest.mark.parametrize('omitnan', [True, False])
+def test_reduce_gradients_every_dim(dev, dn, omitnan):
+    import _reduce_ref as RR
+    R = N().reduce
+    x, rng = _grad_data((5, 70, 6, 33), dn, 31, 0.05 if omitnan else 0.0)
+    if not omitnan:
+        x[1, 5, 2, 7] = np.nan                         # one NaN: var / std propagate it to their slices' gradients
+    worst = 0.0
+    for di, dim in enumerate(_GRAD_DIMS):
+        tr = RR.Truth(x, dim)
+        # keepdim both ways on the scalar and the staged dims, alternating elsewhere; dtype=float64 with keepdim
+        for keepdim in ((False, True) if dim in (1, (0, 3)) else (bool(di % 2),)):
+            for fn, ddof in (('sum', 0), ('mean', 0), ('var', 1), ('var', 0), ('std', 1), ('std', 0)):
+                for odt in ((None, torch.float64) if dn == 'f32' and keepdim else (None,)):
+                    leaf, xin = _leaf(x, dev)
+                    kw = {} if fn in ('sum', 'mean') else {'unbiased': bool(ddof)}
+                    out = getattr(R, fn)(xin, dim, keepdim, omitnan=omitnan, dtype=odt, **kw)
+                    assert out.dtype == (odt or _GDT[dn])
+                    g, gd = _cotangent(out, rng, dev)
+                    (out * gd).sum().backward()
+                    assert leaf.grad.dtype == _GDT[dn]
+                    ref, bound = RR.grad_truth(x, dim, fn, g, ddof, omitnan, tr)
+                    what = (fn, ddof, dim, keepdim, odt)
+                    worst = max(worst, RR.judge_grad(leaf.grad.cpu().numpy(), ref, bound, what))
+                    if omitnan:                        # exactly zero at the omitted positions
+                        assert (leaf.grad.cpu().numpy()[np.isnan(x)] == 0).all(), what
+    print(f'GRAD {dn} omitnan={omitnan}: worst error/bound {worst:.3g}')
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_reduce_gradients_long_axes_and_counts(dev, dn):
+    """reduced lengths that put the forward pass and RED_NANCOUNT on a chunked plan ((3, 70_001): FLAT, 68 chunks;
+    (2, 1025, 3): FLAT, 3 chunks), and the counts of every dim choice, compared exactly"""
+    import _reduce_ref as RR
+    from nitorch_fastmath_amd import _lib
+    R = N().reduce
+    for shape, dims in (((3, 70_001), (1, None)), ((2, 1025, 3), (1, (0, 1))), ((5, 70, 6, 33), _GRAD_DIMS)):
+        x, rng = _grad_data(shape, dn, 37 + len(shape))
+        xd = torch.from_numpy(x).to(dev)
+        for dim in dims:
+            cnt = R._reduce(_lib.RED_NANCOUNT, xd, dim, True, torch.float64)[0].cpu().numpy()
+            ax = None if dim is None else (tuple(dim) if isinstance(dim, tuple) else dim)
+            assert np.array_equal(cnt, (~np.isnan(x)).sum(axis=ax, keepdims=True).astype(np.float64)), (shape, dim)
+        if len(shape) == 4:
+            continue
+        for dim in dims:
+            for fn, ddof in (('sum', 0), ('mean', 0), ('var', 1), ('std', 0)):
+                leaf, xin = _leaf(x, dev)
+                kw = {} if fn in ('sum', 'mean') else {'unbiased': bool(ddof)}
+                out = getattr(R, fn)(xin, dim, omitnan=True, **kw)
+                g, gd = _cotangent(out, rng, dev)
+                (out * gd).sum().backward()
+                ref, bound = RR.grad_truth(x, dim, fn, g, ddof, True)
+                RR.judge_grad(leaf.grad.cpu().numpy(), ref, bound, (shape, fn, dim))
+            for which in ('max', 'min'):
+                leaf, xin = _leaf(x, dev)
+                out = getattr(R, which)(xin, dim, omitnan=True)
+                g, gd = _cotangent(out, rng, dev)
+                (out * gd).sum().backward()
+                ref, _ = RR.pick_truth(x, dim, which, g, True)
+                assert np.array_equal(leaf.grad.cpu().numpy().astype(np.longdouble), ref), (shape, which, dim)
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_reduce_gradients_through_views(dev, dn):
+    """a permuted view (reduced in place through the mapped dims) and a strided slice as input: the gradient
+    arrives in the leaf's own layout"""
+    import _reduce_ref as RR
+    R = N().reduce
+    base, rng = _grad_data((2, 6, 7, 9, 5), dn, 41)
+    views = ((lambda t: t.permute(0, 2, 3, 4, 1), lambda a: a.transpose(0, 2, 3, 4, 1), (-1, (1, 2), (0, 4))),
+             (lambda t: t[:, 1::2, :, ::3], lambda a: a[:, 1::2, :, ::3], (1, (2, 3), None)))
+    for tview, nview, dims in views:
+        xv = nview(base)
+        for dim in dims:
+            for fn, ddof in (('sum', 0), ('mean', 0), ('var', 1), ('std', 1)):
+                leaf, xin = _leaf(base, dev, tview)
+                assert not xin.is_contiguous()
+                kw = {} if fn in ('sum', 'mean') else {'unbiased': bool(ddof)}
+                out = getattr(R, fn)(xin, dim, omitnan=True, **kw)
+                g, gd = _cotangent(out, rng, dev)
+                (out * gd).sum().backward()
+                ref, bound = RR.grad_truth(xv, dim, fn, g, ddof, True)
+                full_ref, full_bound = np.zeros(base.shape, np.longdouble), np.zeros(base.shape, np.longdouble)
+                nview(full_ref)[...] = ref                # entries outside the view get no gradient
+                nview(full_bound)[...] = bound
+                RR.judge_grad(leaf.grad.cpu().numpy(), full_ref, full_bound, (fn, dim))
+            for which in ('max', 'min'):
+                leaf, xin = _leaf(base, dev, tview)
+                out = getattr(R, which)(xin, dim, omitnan=True)
+                g, gd = _cotangent(out, rng, dev)
+                (out * gd).sum().backward()
+                ref, _ = RR.pick_truth(xv, dim, which, g, True)
+                full_ref = np.zeros(base.shape, np.longdouble)
+                nview(full_ref)[...] = ref
+                assert np.array_equal(leaf.grad.cpu().numpy().astype(np.longdouble), full_ref), (which, dim)
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_pick_gradients_ties_and_nans(dev, dn):
+    """max / min / nanmax / nanmin: the returned index is the first occurrence (numpy's argmax / argmin), it gets the
+    whole cotangent; the omitting forms leave NaN positions (an all-NaN slice included) without gradient, the
+    propagating forms send the cotangent to the first NaN"""
+    import _reduce_ref as RR
+    R = N().reduce
+    x, rng = _grad_data((5, 70, 6, 33), dn, 43)
+    x[rng.random(x.shape) < 0.2] = 4.5                 # ties, above most of the data: often the maximum
+    x[rng.random(x.shape) < 0.1] = 0.5                 # and below: often the minimum
+    x[2, :, 3, 7] = np.nan                             # an all-NaN slice for dim 1
+    for omitnan in (True, False):
+        for dim in (1, -1, (1, 2), (0, 3), None):
+            for keepdim in (False, True):
+                for which in ('max', 'min'):
+                    leaf, xin = _leaf(x, dev)
+                    if dim is not None and not isinstance(dim, tuple):
+                        out, idx = getattr(R, which)(xin, dim, keepdim, omitnan=omitnan, return_indices=True)
+                    else:
+                        out, idx = getattr(R, which)(xin, dim, keepdim, omitnan=omitnan), None
+                    g, gd = _cotangent(out, rng, dev)
+                    (out * gd).sum().backward()
+                    ref, arg = RR.pick_truth(x, dim, which, g, omitnan)
+                    what = (which, omitnan, dim, keepdim)
+                    assert np.array_equal(leaf.grad.cpu().numpy().astype(np.longdouble), ref), what
+                    if idx is not None:
+                        assert np.array_equal(idx.cpu().numpy().reshape(-1), arg), what
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_median_gradients(dev, dn):
+    """ties and omitnan=True through the rows kernel, >= 4096 rows of a middle dim through the per-lane kernel,
+    a row longer than 1024 (radix selection): the whole cotangent at the returned index, which holds the median"""
+    R = N().reduce
+    rng = np.random.default_rng(47)
+    dt = np.float32 if dn == 'f32' else np.float64
+    for shape, dim, omitnan in (((40, 33), 1, True), ((40, 33), 1, False), ((2, 9, 5000), 1, True), ((3, 1500), 1, True),
+                                ((3, 1500), 1, False)):
+        x = np.round(rng.standard_normal(shape) * 4).astype(dt) / 4 + 0        # a grid of values: many ties (no -0)
+        if omitnan:
+            x[rng.random(shape) < 0.1] = np.nan
+        leaf, xin = _leaf(x, dev)
+        out, idx = R.median(xin, dim, omitnan=omitnan, return_indices=True)
+        g, gd = _cotangent(out, rng, dev)
+        (out * gd).sum().backward()
+        xs = np.moveaxis(x, dim, -1)
+        srt = np.sort(xs, -1)                                                # NaNs last
+        cnt = (~np.isnan(xs)).sum(-1)
+        med = np.take_along_axis(srt, ((cnt - 1) // 2)[..., None], -1)[..., 0]     # the lower median
+        assert np.array_equal(out.detach().cpu().numpy(), med), (shape, omitnan)
+        first = (xs == med[..., None]).argmax(-1)                            # its first occurrence
+        assert np.array_equal(idx.cpu().numpy(), first), (shape, omitnan)
+        ref = np.zeros(xs.shape)
+        np.put_along_axis(ref, first[..., None], g[..., None], -1)
+        assert np.array_equal(leaf.grad.cpu().numpy().astype(np.float64), np.moveaxis(ref, -1, dim)), (shape, omitnan)
+
+
+def test_reduce_gradients_degenerate_slices_and_out(dev):
+    """std of a constant slice and var with n = ddof give what torch gives on the CPU (0 where std == 0: torch masks
+    the division; NaN for n = ddof), no exception; out= with a leaf that requires grad still raises"""
+    R = N().reduce
+    x = torch.tensor([[2.0, 2.0, 2.0, 2.0], [1.0, 2.0, 3.0, 5.0]], dtype=torch.float64)
+    for ours, ref, kw in ((R.std, torch.std, {}), (R.var, torch.var, {}), (R.std, torch.std, {'unbiased': False})):
+        xc, xd = x.clone().requires_grad_(), x.to(dev).requires_grad_()
+        ref(xc, dim=1, **kw).sum().backward()
+        ours(xd, dim=1, **kw).sum().backward()
+        got = xd.grad.cpu()
+        assert torch.equal(torch.isnan(got), torch.isnan(xc.grad)) and torch.equal(torch.isinf(got), torch.isinf(xc.grad))
+        assert torch.allclose(torch.nan_to_num(got, 0, 0, 0), torch.nan_to_num(xc.grad, 0, 0, 0), rtol=1e-13, atol=0)
+    one = x[:, :1].contiguous()                          # n = ddof = 1
+    xc, xd = one.clone().requires_grad_(), one.to(dev).requires_grad_()
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        torch.var(xc, dim=1).sum().backward()
+    R.var(xd, dim=1).sum().backward()
+    got = xd.grad.cpu()
+    assert torch.equal(torch.isnan(got), torch.isnan(xc.grad)) and torch.equal(torch.isinf(got), torch.isinf(xc.grad))
+    leaf = x.to(dev).requires_grad_()
+    for fn in (R.max, R.min, R.median, R.nanmax):
+        with pytest.raises(RuntimeError):
+            fn(leaf, dim=1, out=torch.empty(2, dtype=torch.float64, device=dev))

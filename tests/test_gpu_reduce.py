@@ -604,3 +604,118 @@ def test_median_large(dev):
     ref = torch.median(f.reshape(3, 8, -1), dim=-1).values
     assert torch.equal(v, ref) and i.shape == (3, 8, 2)
     assert torch.equal(f[torch.arange(3)[:, None], torch.arange(8)[None], i[..., 0], i[..., 1]], v)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Moments where the shift matters: offset + N(0, 1) data, per-slice verdicts against the longdouble two-pass truth
+# and the derived bounds of tests/_reduce_ref.py (the shift K of MomAcc / pick_shift only matters when |mean| is far
+# above the standard deviation; the tests above use data around 0 and bars relative to mean(x^2)).
+#
+# (shape, dim) -> plan of plan_dim (nfm_reduce_dim.hip) for float32 / float64, 16-byte aligned base:
+MOMENT_ROUTES = [
+    ((1000, 8), 1),        # GROUP, inner 1, one vector per lane (IT 1; 2 / 4 lanes per slab)
+    ((300, 100), 1),       # GROUP, inner 1, 8 lanes per slab, IT 4 / 7 (25 / 50 vectors): the lane's own shift
+    ((600, 4, 4), 1),      # GROUP with columns, IT 1 (one element per lane and column)
+    ((4, 60, 4), 1),       # GROUP with columns, IT 8 / 15 (pick_shift per column, then the lane's batches)
+    ((33, 2000), 1),       # FLAT, inner 1 (COMB_ALL), one chunk
+    ((3, 100_001), 1),     # FLAT scalar (odd slab), 92 chunks: partial records folded by the wavefront-per-output kernel
+    ((5, 700, 2), 1),      # FLAT, COMB_SUBV (float32: 2 columns inside a 4-vector) / COMB_SHFL (float64)
+    ((7, 300, 8), 1),      # FLAT, COMB_SHFL
+    ((3, 400, 5), 1),      # FLAT, COMB_LDS (A = 60 lanes)
+    ((2, 300, 1000), 1),   # COL vector, 18 chunks of the reduced axis (lane-per-output fold)
+    ((3, 50, 1001), 1),    # COL scalar, one chunk
+    ((1, 3000, 260), 1),   # COL vector, 177 chunks (wavefront-per-output fold)
+]
+# non-adjacent dims: raw moments of the last run + the merge of _stat_staged
+#   (0, 2, 3, 4): _moments over (2, 3, 4) = (12, 495, 1): GROUP scalar, IT 16 / 31;  (1, 3): (108, 11, 5): COL scalar
+STAGED_SHAPE, STAGED_DIMS = (3, 4, 9, 11, 5), ((0, 2, 3, 4), (1, 3))
+# channel-last view of a channel-first (2, 6, 7, 9, 5) field, reduced in place through the mapped dims:
+#   -1 -> base dim 1: (2, 6, 315) COL scalar;  (1, 2) -> base dims (2, 3): (12, 63, 5) FLAT scalar, COMB_LDS
+PERM_BASE, PERM, PERM_DIMS = (2, 6, 7, 9, 5), (0, 2, 3, 4, 1), (-1, (1, 2))
+FULL_SIZES = (9, 1000, (1 << 20) + 77)     # dim=None: GROUP / GROUP (f32), FLAT (f64) / FLAT chunked; _moments: the
+                                           # two-kernel full reduction of nfm_reduce.hip (head, vectors, tail)
+_TORCH_DT = {'f32': torch.float32, 'f64': torch.float64}
+
+
+def _judge_moment_functions(xd, tr, dim, dn, tag, ratios, strict=True):
+    """every statistic of one input: a verdict for every output slice (tr.judge asserts), worst ratios recorded"""
+    import _reduce_ref as RR
+    r = R()
+    odt = RR.DT[dn]
+
+    def rec(name, ratio):
+        ratios[name] = max(ratios.get(name, 0.0), ratio)
+
+    def host(v):
+        return v.cpu().numpy()
+
+    rec('nanmean', tr.judge(host(r.nanmean(xd, dim)), 'mean', 0, True, odt, tag, strict))
+    rec('mean', tr.judge(host(r.mean(xd, dim)), 'mean', 0, False, odt, tag, strict))
+    for unb in (True, False):
+        rec('nanvar', tr.judge(host(r.nanvar(xd, dim, unbiased=unb)), 'var', int(unb), True, odt, tag, strict))
+        rec('nanstd', tr.judge(host(r.nanstd(xd, dim, unbiased=unb)), 'std', int(unb), True, odt, tag, strict))
+        rec('var', tr.judge(host(r.var(xd, dim, unbiased=unb)), 'var', int(unb), False, odt, tag, strict))
+        rec('std', tr.judge(host(r.std(xd, dim, unbiased=unb)), 'std', int(unb), False, odt, tag, strict))
+    if dn == 'f32':
+        f64 = torch.float64
+        rec('nanmean64', tr.judge(host(r.nanmean(xd, dim, dtype=f64)), 'mean', 0, True, np.float64, tag, strict))
+        rec('nanvar64', tr.judge(host(r.nanvar(xd, dim, dtype=f64)), 'var', 1, True, np.float64, tag, strict))
+        rec('nanstd64', tr.judge(host(r.nanstd(xd, dim, unbiased=False, dtype=f64)), 'std', 0, True, np.float64, tag, strict))
+        rec('var64', tr.judge(host(r.var(xd, dim, dtype=f64)), 'var', 1, False, np.float64, tag, strict))
+    n, s, q, k, _ = r._moments(xd, dim, False)
+    rec('moments', RR.judge_moments(tr, host(n), host(s), host(q), host(k), tag, strict))
+    return tr.n.size
+
+
+def _moment_inputs(dn, offset, variant, dev):
+    """(tag, numpy array, device tensor, dim) of every route; the truth is shared by the aligned and the
+    misaligned tensor of an array"""
+    import _reduce_ref as RR
+    seed = 0
+    for shape, dim in MOMENT_ROUTES:
+        seed += 1
+        for x in RR.make_batches(shape, dim, dn, offset, variant, 100 * seed):
+            flat = np.concatenate([np.zeros(1, x.dtype), x.reshape(-1)])
+            yield f'{shape} dim={dim}', x, dim, (t(x, dev), t(flat, dev)[1:].reshape(shape))   # + one element off 16 bytes
+    for dim in STAGED_DIMS:
+        seed += 1
+        for x in RR.make_batches(STAGED_SHAPE, dim, dn, offset, variant, 100 * seed):
+            yield f'staged {dim}', x, dim, (t(x, dev),)
+    inv = list(np.argsort(PERM))
+    view_shape = tuple(PERM_BASE[p] for p in PERM)
+    for dim in PERM_DIMS:
+        seed += 1
+        for x in RR.make_batches(view_shape, dim, dn, offset, variant, 100 * seed):
+            xd = t(x.transpose(inv), dev).permute(PERM)
+            assert not xd.is_contiguous() and tuple(xd.shape) == view_shape
+            yield f'permuted view {dim}', x, dim, (xd,)
+    for n in FULL_SIZES:
+        seed += 1
+        batches = RR.make_batches((n + 3,), None, dn, offset, variant, 100 * seed)
+        if n > 100_000:
+            batches = [batches[3], batches[5], batches[-1]]      # the constant, the outlier and the ordinary array
+        for bi, x in enumerate(batches):
+            xd = t(x, dev)
+            for off in ((0, 1, 3) if (n <= 100_000 or bi == 2) else (0,)):
+                yield f'full n={n} from {off}', x[off:off + n], None, (xd[off:off + n],)
+
+
+@pytest.mark.parametrize('variant', ['clean', 'nan5', 'border'])
+@pytest.mark.parametrize('dn,offset', [('f32', 0.0), ('f32', 3e4), ('f32', 1e6), ('f64', 0.0), ('f64', 1e8)])
+def test_moments_of_offset_data(dev, dn, offset, variant):
+    """nanmean / nanvar / nanstd, their propagating forms, dtype=float64 and the raw moments on every route,
+    with 5 % NaNs and behind a NaN border of 8..40 positions, special slices included; no slice is left out.
+
+    On the parent of the commit that added this test the 'border' and 'nan5' cases failed at float32 offset 1e6 and
+    float64 offset 1e8 (a slice that starts with 8 NaNs, or a lane whose first vector is all NaN, was folded with
+    K = 0), and the staged route failed at float64 offset 1e8 in every variant (profiles/reduce_accuracy.md)."""
+    import _reduce_ref as RR
+    assert RR.hp_ok()
+    ratios, judged = {}, 0
+    for tag, x, dim, tensors in _moment_inputs(dn, offset, variant, dev):
+        tr = RR.Truth(x, dim)
+        for xd in tensors:
+            judged += _judge_moment_functions(xd, tr, dim, dn, tag, ratios)
+    print(f'MOMENTS {dn} offset={offset:g} {variant}: {judged} slices judged; worst error/bound ' +
+          ' '.join(f'{k}={v:.3g}' for k, v in sorted(ratios.items())))
+    assert judged > 10_000 and max(ratios.values()) <= 1.0
