@@ -253,9 +253,29 @@ __device__ __forceinline__ void div2_cr(double x, double y, double n, double &qx
 template <typename T>
 __device__ __forceinline__ void givens1(T x, T y, T &c, T &s);
 
+// givens1 on the pair divided by its larger magnitude (IEEE division: one component becomes +-1 exactly), so that
+// the sum of squares lies in [1, 2] whatever the size of the pair.  givens1 itself squares x and y as they are:
+// for a pair below 2^-63 (float32) inside a unit-scale matrix -- what repeated, clustered and rank-one spectra
+// leave behind -- the squares are denormal or zero, c^2 + s^2 is off by per cents and the eigenvectors lose
+// orthogonality.  That is upstream's arithmetic and stays in the reference-order sweeps; the fast sweeps fall
+// back to this form.  Axis-aligned pairs stay exact (x / |x| = +-1, y = 0: sqrt(1) = 1), (0, 0) gives (1, 0).
+template <typename T>
+__device__ __forceinline__ void givens_scaled1(T x, T y, T &c, T &s)
+{
+#pragma clang fp contract(off)
+    const T ax = fabs_(x), ay = fabs_(y);
+    const T m = ax > ay ? ax : ay;
+    const bool z = m == T(0);
+    const T d = z ? T(1) : m;
+    const T xs = x / d, ys = y / d;
+    const T nrm = sqrt_(xs * xs + ys * ys);
+    c = z ? T(1) : xs / nrm;
+    s = z ? T(0) : -(ys / nrm);
+}
+
 // sweep form of the same rotation (policy above).  The fast values are computed unconditionally;
 // only if SOME lane of the wavefront is outside the safe range (a uniform vote: no exec-mask
-// juggling on the common path) the IEEE form runs as well and those lanes take its result.
+// juggling on the common path) the IEEE form (givens_scaled1) runs as well and those lanes take its result.
 template <typename T>
 __device__ __forceinline__ void givens_fast1(T x, T y, T &c, T &s)
 {
@@ -270,7 +290,7 @@ __device__ __forceinline__ void givens_fast1(T x, T y, T &c, T &s)
     s = -(y * inv);
     if (__builtin_expect(__any(!ok), 0)) {
         T c2, s2;
-        givens1<T>(x, y, c2, s2);
+        givens_scaled1<T>(x, y, c2, s2);
         c = ok ? c : c2;
         s = ok ? s : s2;
     }
@@ -384,10 +404,17 @@ __device__ __forceinline__ T householder1(T (&x)[Dim<NT>::MAX], int m, int basis
         const T rhof = rho * nrm;
         const T inv = rsq_nr(ss2);
         if (__builtin_expect(__any(!ok), 0)) {
+            // the IEEE form on x divided by its largest magnitude (the reflector does not depend on the scale,
+            // rho is scaled back): its sums of squares then lie in [1, 4 m], wherever x's own would underflow
             T y[Dim<NT>::MAX];
+            T big = T(0);
 #pragma unroll
-            for (int i = 0; i < Dim<NT>::MAX; ++i) y[i] = x[i];
-            const T rho2 = householder1<T, NT, false>(y, m, basis);
+            for (int i = 0; i < Dim<NT>::MAX; ++i)
+                if (i < m) big = fabs_(x[i]) > big ? fabs_(x[i]) : big;
+            big = (big > T(0) && finite_(big)) ? big : T(1); // zero vectors, inf: as they are (NaN is never the maximum)
+#pragma unroll
+            for (int i = 0; i < Dim<NT>::MAX; ++i) y[i] = x[i] / big;
+            const T rho2 = householder1<T, NT, false>(y, m, basis) * big;
 #pragma unroll
             for (int i = 0; i < Dim<NT>::MAX; ++i)
                 if (i < m) x[i] = ok ? ((i == basis) ? x[i] - rhof : x[i]) * inv : y[i];
@@ -788,9 +815,12 @@ __device__ __forceinline__ void qr_explicit_band1(T (&d)[Dim<NT>::MAX], T (&l)[D
                     if (i < m) d[i] += sigma;
                 const T bb = fabs_(l[m - 2]), a0 = fabs_(d[m - 1]), a1 = fabs_(d[m - 2]);
                 const T sos_lower = bb * bb, sos_diag = a0 * a0 + a1 * a1;
-                // `<=` (upstream: `<`) and the NaN test only matter when nothing can change any
-                // more: a zero off-diagonal (diagonal or zero blocks, padding lanes of the last
-                // tile) or NaNs would otherwise spin through all max_iter identical iterations
+                // `<=` (upstream: `<`) and the NaN test: a zero off-diagonal (diagonal or zero blocks, padding
+                // lanes of the last tile) or NaNs cannot change any more and would otherwise spin through all
+                // max_iter identical iterations.  `<=` also fires when BOTH squares underflow to zero with the
+                // entries themselves non-zero (0 <= tol * 0): the stage then deflates unconverged.  The scale
+                // rule (eig_prescale1) keeps whole records out of that range; a tiny block inside a unit-scale
+                // record can still meet it (tests/_eig_ref.py, REFERENCE_EXCEEDS)
                 if ((double)sos_lower <= tol * (double)sos_diag || sos_lower != sos_lower) {
                     l[m - 2] = T(0); // h[m-1][:m-1] = 0: the only entry of that row the band holds
                     break;
@@ -949,11 +979,15 @@ __device__ __forceinline__ void qr_fast_band1(T (&d)[Dim<NT>::MAX], T (&e)[Dim<N
     // The reference deflates when e^2 < tol (d0^2 + d1^2) with tol = 1e-32 by default: |e| < 1e-16 |d|,
     // the working precision of float64 -- but eight orders below float32's, where it costs one more
     // sweep per eigenvalue just to square an off-diagonal that is already below half an ulp.  The fast
-    // sweeps floor the tolerance at the working precision of the dtype, |e| <= eps/4 |d| (the neglected
-    // entry moves an eigenvalue by at most |e|: a quarter of an ulp); a larger caller tolerance is kept.
-    const double floor_ = sizeof(T) == 4 ? 0x1p-52 : 0x1p-110; // (eps / 4)^2, eps = 2^-24 / 2^-53
+    // sweeps floor the tolerance at the working precision of the dtype, |e| <= eps |(d0, d1)| with eps the unit
+    // roundoff (LAPACK's xSTEQR test; the neglected entry moves an eigenvalue by at most |e|: half an ulp); a
+    // larger caller tolerance is kept.  Not lower: inside a cluster of eigenvalues that agree to working precision
+    // every sweep re-creates off-diagonals of the size of d's own rounding, eps |d|, so a floor of (eps/4)^2 was
+    // reached by luck only -- such stages ran all max_iter sweeps, and a thousand sweeps of rotations cost the
+    // eigenvectors their orthogonality (70 n eps at n = 16: profiles/eig_sym_accuracy.md).
+    const double floor_ = sizeof(T) == 4 ? 0x1p-48 : 0x1p-106; // eps^2, eps = 2^-24 / 2^-53
     tol = tol > floor_ ? tol : floor_;
-    const T tol_t = (T)tol, stuck_t = (T)(tol * 1e-3);
+    const T tol_t = (T)tol, stuck_t = (T)(tol * 1e-3), rtol_t = (T)__builtin_sqrt(tol);
     if (WITH_U) {
 #pragma unroll
         for (int i = 0; i < MX; ++i)
@@ -977,10 +1011,14 @@ __device__ __forceinline__ void qr_fast_band1(T (&d)[Dim<NT>::MAX], T (&e)[Dim<N
                 tri_sweep_fast1<T, NT, WITH_U>(d, e, u, n, m, sigma);
                 const T bb = fabs_(e[m - 2]), a0 = fabs_(d[m - 1]), a1 = fabs_(d[m - 2]);
                 const T sos_lower = bb * bb, sos_diag = a0 * a0 + a1 * a1;
-                // `<=` (upstream: `<`) and the NaN test only matter when nothing can change any
-                // more: a zero off-diagonal (diagonal or zero blocks, padding lanes of the last
-                // tile) or NaNs would otherwise spin through all max_iter identical iterations
-                const bool conv = sos_lower <= tol_t * sos_diag; // in T: tol_t >= (eps/4)^2 is a normal number
+                // `<=` (upstream: `<`) and the NaN test: a zero off-diagonal (diagonal or zero blocks, padding
+                // lanes of the last tile) or NaNs cannot change any more and would otherwise spin through all
+                // max_iter identical iterations.
+                // in T: tol_t >= eps^2 is a normal number.  Where tol_t * sos_diag leaves the normal range (a
+                // block far below the matrix's scale) the squares say nothing -- 0 <= tol * 0 would deflate whatever
+                // e is -- and the magnitudes are compared instead: |e| <= sqrt(tol) max(|d0|, |d1|)
+                const T dmax = a0 > a1 ? a0 : a1;
+                const bool conv = tol_t * sos_diag < FastRange<T>::lo ? bb <= rtol_t * dmax : sos_lower <= tol_t * sos_diag;
                 if (conv || sos_lower != sos_lower) {
                     e[m - 2] = T(0);
                     break;
@@ -1039,6 +1077,120 @@ __device__ __forceinline__ void reflect_left1(MA &a, int n, int k0, const T (&w)
         }
 }
 
+// THE SCALE RULE of eig_sym (not upstream's; the CPU restatement's `eig_prescale1` is the same rule bit for bit).
+// The sweeps square matrix entries in T -- Householder's sum of squares, Wilkinson's b^2, Givens' x^2 + y^2, the
+// convergence test e^2 <= tol (d0^2 + d1^2) -- so their range is the square root of T's: outside it the squares
+// underflow or overflow, and the iteration deflates at once on 0 <= tol * 0 (returning the diagonal) or returns
+// NaN.  A record whose largest entry has an exponent outside the window below is therefore multiplied by the exact
+// power of two that brings that entry into [1, 2), solved, and its eigenvalues are scaled back (v_ldexp: one
+// rounding, and only where the result is subnormal); eigenvectors do not depend on the scale.  Inside the window
+// the cost is one maximum over the triangle, one wavefront vote and (register kernels) a v_ldexp by 0 per entry of
+// the triangle, and the bits are those of the unscaled solve.
+// Zero records and records with an inf or a NaN in the triangle are left alone.
+// The window is the widest in which the unscaled reference-order arithmetic meets the per-record bars of
+// tests/_eig_ref.py, with a margin (profiles/eig_sym_accuracy.md).
+template <typename T>
+struct EigWindow;
+template <>
+struct EigWindow<float> {
+    static constexpr int lo = -50, hi = 56;
+};
+template <>
+struct EigWindow<double> {
+    static constexpr int lo = -480, hi = 480;
+};
+__device__ __forceinline__ float ldexp_t(float x, int k) { return __builtin_ldexpf(x, k); }
+__device__ __forceinline__ double ldexp_t(double x, int k) { return __builtin_ldexp(x, k); }
+// the (high) dword of |x|: sign off, exponent field on top -- ordered like |x| itself as an unsigned integer, and
+// all that the window test needs (NaN sorts above inf)
+__device__ __forceinline__ unsigned abs_hi(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned abs_hi(double x)
+{
+    return (unsigned)(__builtin_bit_cast(unsigned long long, x) >> 32) & 0x7fffffffu;
+}
+template <typename T>
+struct EigBits;
+template <>
+struct EigBits<float> {
+    static constexpr unsigned lo = (unsigned)(EigWindow<float>::lo + 127) << 23;
+    static constexpr unsigned hi = ((unsigned)(EigWindow<float>::hi + 128) << 23) - 1u;
+    static constexpr unsigned inf = 0x7f800000u;
+};
+template <>
+struct EigBits<double> {
+    static constexpr unsigned lo = (unsigned)(EigWindow<double>::lo + 1023) << 20;
+    static constexpr unsigned hi = ((unsigned)(EigWindow<double>::hi + 1024) << 20) - 1u;
+    static constexpr unsigned inf = 0x7ff00000u;
+};
+// exponent e of mx > 0 (mx in [2^e, 2^(e+1)), subnormals included)
+__device__ __forceinline__ int exponent_of(float mx)
+{
+    const unsigned b = __builtin_bit_cast(unsigned, mx);
+    const int E = (int)(b >> 23);
+    return E ? E - 127 : (31 - __builtin_clz(b | 1u)) - 149;
+}
+__device__ __forceinline__ int exponent_of(double mx)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, mx);
+    const int E = (int)(b >> 52);
+    return E ? E - 1023 : (63 - __builtin_clzll(b | 1ull)) - 1074;
+}
+// visit the lower triangle (diagonal included) of the leading n x n block: f(a[i][j]).  Compile-time orders
+// recurse over a literal linear index instead of looping: the visits sit inside a uniform branch, where a loop nest
+// is unrolled too late for the register matrix to be split into scalars (it went to scratch memory).
+constexpr int tri_row(int idx) { int i = 0; while ((i + 1) * (i + 2) / 2 <= idx) ++i; return i; }
+template <int MX, int IDX = 0, class MA, class F>
+__device__ __forceinline__ void for_lower_static(MA &a, F &f)
+{
+    if constexpr (IDX < MX * (MX + 1) / 2) {
+        constexpr int i = tri_row(IDX), j = IDX - i * (i + 1) / 2;
+        f(a[i][j]);
+        for_lower_static<MX, IDX + 1>(a, f);
+    }
+}
+template <int NT, class MA, class F>
+__device__ __forceinline__ void for_lower(MA &a, int n, F f)
+{
+    if constexpr (NT > 0) {
+        for_lower_static<NT>(a, f);
+    } else {
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j <= i; ++j) f(a[i][j]);
+    }
+}
+// returns the shift k: the lane's record was multiplied by 2^k (0: untouched).  The common path is an integer
+// maximum of the entries' high dwords and one unsigned compare; the exact maximum, its exponent and the scaling run
+// only when some lane of the wavefront is outside the window (float64: or has a high dword of zero, which a record
+// of zeros shares with one below 2^-1042).
+template <typename T, int NT, class MA>
+__device__ __forceinline__ int eig_prescale1(MA &a, int n)
+{
+    unsigned h = 0u;
+    for_lower<NT>(a, n, [&h](const T &x) {
+        const unsigned v = abs_hi(x);
+        h = v > h ? v : h;
+    });
+    const bool out = (h - EigBits<T>::lo) > (EigBits<T>::hi - EigBits<T>::lo) && (sizeof(T) == 8 || h != 0u);
+    int k = 0;
+    const bool any_out = __any(out);
+    if (__builtin_expect(any_out, 0)) {
+        T mx = T(0);
+        for_lower<NT>(a, n, [&mx](const T &x) {
+            const T v = fabs_(x);
+            mx = (v > mx) ? v : mx;
+        });
+        // a record with an inf or a NaN, or of zeros, stays as it is
+        k = (out && h < EigBits<T>::inf && mx > T(0)) ? -exponent_of(mx) : 0;
+        const int e = -k;
+        k = (e >= EigWindow<T>::lo && e <= EigWindow<T>::hi) ? 0 : k; // (float64 records that only looked outside)
+    }
+    // A register matrix is scaled OUTSIDE the branch, by 2^0 on the common path (n (n + 1) / 2 v_ldexp, the identity):
+    // stores to it under the uniform branch kept the compiler from splitting it into registers (the matrix went to
+    // scratch memory in 35 kernels).  An LDS image is only touched when a lane asks for it.
+    if (NT > 0 || any_out) for_lower<NT>(a, n, [k](T &x) { x = ldexp_t(x, k); });
+    return k;
+}
+
 // _fwd_eig_sym :665-681.  `a` holds the symmetric input in its LOWER triangle (the caller mirrors the
 // requested one on load; the upper triangle is never read); `up` is where the reflectors go (WITH_U).  On
 // return vals = eigenvalues in deflation order, and for WITH_U the columns of u are the eigenvectors.
@@ -1047,6 +1199,7 @@ __device__ __forceinline__ void eig_sym1(MA &a, MU &u, MP &up, T (&vals)[Dim<NT>
 {
     constexpr int MX = Dim<NT>::MAX;
     constexpr bool FM = FAST && FastSweeps<T>::on;
+    const int shift = eig_prescale1<T, NT>(a, n); // the scale rule above: both arithmetic modes, every kernel form
     hessenberg_sym1<T, NT, WITH_U, FAST, !FAST, false>(a, n, up);
     T e[MX];
 #pragma unroll
@@ -1058,6 +1211,10 @@ __device__ __forceinline__ void eig_sym1(MA &a, MU &u, MP &up, T (&vals)[Dim<NT>
     }
     if constexpr (FM) qr_fast_band1<T, NT, WITH_U>(vals, e, u, n, max_iter, tol);
     else qr_explicit_band1<T, NT, WITH_U>(vals, e, u, n, max_iter, tol);
+    if (__builtin_expect(__any(shift != 0), 0)) {
+#pragma unroll
+        for (int i = 0; i < MX; ++i) vals[i] = ldexp_t(vals[i], -shift);
+    }
     if (WITH_U) {
         // householder_apply_(u, q, side='left', inverse=True): reflectors in reverse order
 #pragma unroll

@@ -23,11 +23,24 @@ SIGNS (the division and square root sequences are the IEEE ones without their ra
 taken on a wavefront vote that every operand is in range; anything else takes the full sequence);
 `'fast'` (opt-in) runs the QR sweeps on v_rsq + Newton steps with fma contraction, diagonalises the
 last 2x2 block in closed form (one Jacobi rotation) and never deflates below the working precision
-of the dtype (`tol` is floored at (eps/4)^2: float32 stops at |e| <= 1.5e-8 |d| where the
+of the dtype (`tol` is floored at eps^2, eps the unit roundoff: float32 stops at |e| <= 6e-8 |d| where the
 reference's default 1e-32 asks for 1e-16 |d|) -- 2-3x the throughput and the same accuracy
 against the exact eigenvalues, but the deflation order and the eigenvector signs differ from the
 reference's for a share of the matrices (float32 3x3: 2 %, 8x8: 35 %; the number of sweeps a stage
 takes decides where the remaining eigenvalues land) and float32 values by up to 1.4e-6.
+
+Scale.  The sweeps square matrix entries in the value type, so on their own they cover the square root of
+its range.  `eig_sym` (both modes) therefore scales a record whose largest entry, over the triangle that
+is read, lies outside [2^-50, 2^57) (float64: [2^-480, 2^481)) by the exact power of two that brings that
+entry into [1, 2), and scales the eigenvalues back (one rounding, only where the result is subnormal);
+inside the window nothing changes, bit for bit.  Every finite input, subnormal ones included, is solved to
+a few n eps |A|_2 per record (tests/_eig_ref.py).  The other entry points of this module keep upstream's range.
+
+Hard spectra.  `'reference'` is upstream's arithmetic, with its limits: `tol = 1e-32` is out of float32's
+reach on repeated or clustered eigenvalues (those stages run all `max_iter` sweeps) and its rotations
+normalise by an unscaled sum of squares, so float32 eigenvectors of such spectra lose orthogonality
+(16-92 n eps at n >= 6; tests/_eig_ref.py REFERENCE_EXCEEDS lists the cells).  Use `arithmetic='fast'` for
+repeated or clustered spectra in float32: it is held to 16 n eps in every cell.
 """
 __all__ = [
     'eig_sym',
@@ -111,7 +124,7 @@ def eig_sym(a, compute_u=False, upper=True, inplace=False, check_finite=True, ma
     check_finite : `bool`, default=True
     max_iter : `int`, default=1024
     tol : `float`, default=1e-32
-        deflate when e^2 <= tol (d0^2 + d1^2); `arithmetic='fast'` uses max(tol, (eps/4)^2)
+        deflate when e^2 <= tol (d0^2 + d1^2); `arithmetic='fast'` uses max(tol, eps^2), eps = 2^-24 / 2^-53
     arithmetic : `{'reference', 'fast'}`, keyword-only, default=`SWEEP_ARITHMETIC` (`'reference'`)
         extension, see the module docstring: `'reference'` reproduces the reference CPU path bit
         for bit (deflation order and eigenvector signs included); `'fast'` trades that for speed.

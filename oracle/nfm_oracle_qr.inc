@@ -196,8 +196,12 @@ static inline void FN(qr_explicit1)(int N, T *h, T *u, int max_iter, double tol,
             T bb = FABS(h[(m - 1) * N + (m - 2)]), a0 = FABS(h[(m - 1) * N + (m - 1)]);
             T a1 = FABS(h[(m - 2) * N + (m - 2)]);
             T sos_lower = bb * bb, sos_diag = a0 * a0 + a1 * a1;
-            /* `<=` (upstream `<`) and the NaN test: a zero off-diagonal or NaNs cannot change any
-               more; upstream spins through max_iter identical iterations there (same result) */
+            /* `<=` (upstream `<`) and the NaN test: a zero off-diagonal or NaNs cannot change any more;
+               upstream spins through max_iter identical iterations there (same result).  `<=` also fires
+               when BOTH squares underflow to zero with the entries themselves non-zero (0 <= tol * 0): the
+               stage then deflates unconverged.  The scale rule of eig_prescale1 keeps whole records out
+               of that range; tiny blocks inside a unit-scale record can still meet it
+               (tests/_eig_ref.py REFERENCE_EXCEEDS). */
             if ((double)sos_lower <= tol * (double)sos_diag || sos_lower != sos_lower) {
                 for (int j = 0; j < m - 1; ++j) h[(m - 1) * N + j] = (T)0;
                 break;
@@ -211,16 +215,49 @@ static inline void FN(qr_explicit1)(int N, T *h, T *u, int max_iter, double tol,
     }
 }
 
+/* The scale rule of eig_sym (not upstream's; shared bit for bit with nfm_qr_core.hpp `eig_prescale1`).
+ * The sweeps square matrix entries in T (Householder's sum of squares, Wilkinson's b^2, Givens' x^2 + y^2, the
+ * convergence test e^2 <= tol (d0^2 + d1^2)), so their range is the square root of T's: outside it the squares
+ * underflow or overflow and the iteration deflates at once on 0 <= tol * 0, or returns NaN.  A record whose
+ * largest entry (over the triangle that is read) has an exponent outside the window [lo, hi] is therefore scaled
+ * by the exact power of two that brings that entry into [1, 2), solved, and its eigenvalues are scaled back (one
+ * rounding, and only where the result is subnormal); the eigenvectors do not depend on the scale.  Inside the
+ * window nothing is touched: the same bits as without the rule.  Zero records and records with an inf or a
+ * NaN in that triangle are left alone.
+ * Returns the shift k (entries were multiplied by 2^k), 0 for none. */
+#define NFM_EIG_WINDOW_LO (sizeof(T) == 4 ? -50 : -480)
+#define NFM_EIG_WINDOW_HI (sizeof(T) == 4 ? 56 : 480)
+static inline int FN(eig_prescale1)(int N, T *a, int upper)
+{
+    T mx = (T)0;
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j <= i; ++j) {
+            T v = FABS(upper ? a[j * N + i] : a[i * N + j]);
+            if (!ISFINITE(v)) return 0;
+            mx = (v > mx) ? v : mx;
+        }
+    if (!(mx > (T)0)) return 0;
+    int e;
+    (void)frexp((double)mx, &e); /* mx = f 2^e, f in [0.5, 1): exact for both types, subnormals included */
+    e -= 1;                      /* mx in [2^e, 2^(e+1)) */
+    if (e >= NFM_EIG_WINDOW_LO && e <= NFM_EIG_WINDOW_HI) return 0;
+    for (int i = 0; i < N * N; ++i) a[i] = (T)ldexp((double)a[i], -e); /* exact, or one rounding into the subnormals */
+    return -e;
+}
+
 /* _fwd_eig_sym :665-681 */
 static inline void FN(eig_sym1)(int N, T *a, int upper, int compute_u, int max_iter, double tol, T *vals,
                                 T *vecs, int *sweeps)
 {
     T upack[NFM_MAXM * NFM_MAXM];
+    const int shift = FN(eig_prescale1)(N, a, upper);
     FN(hessenberg_sym1)(N, a, upper, 1, compute_u ? upack : NULL);
     FN(qr_explicit1)(N, a, compute_u ? vecs : NULL, max_iter, tol, sweeps);
     if (compute_u) /* householder_apply_(u, q, side='left', inverse=True): reflectors in reverse */
         for (int k = N - 3; k >= 0; --k) FN(householder_apply1)(N, N - k - 1, vecs, upack + k * (N - 1), 1, 0);
     for (int i = 0; i < N; ++i) vals[i] = a[i * N + i];
+    if (shift != 0)
+        for (int i = 0; i < N; ++i) vals[i] = (T)ldexp((double)vals[i], -shift);
 }
 
 /* ------------------------------- batch drivers ------------------------------- */

@@ -20,6 +20,7 @@ import torch
 from conftest import relerr
 from test_gpu_qr import GpuQ, Q, t, n_
 import _qr_large_ref as R
+import _eig_ref as E
 
 pytestmark = pytest.mark.gpu
 INT = {torch.float32: torch.int32, torch.float64: torch.int64}
@@ -160,6 +161,8 @@ def test_range_votes(dev, oracle, dn, n, form):
     assert R.same_bits(got, ref), np.argwhere(~((got == ref) | (np.isnan(got) & np.isnan(ref))))[:8]
     gv, gu = F.eig_sym(a, True)
     assert R.same_bits(gv, rv) and R.same_bits(gu, ru)
+    # right at every scale, record by record (tests/_eig_ref.py), not only equal to the oracle
+    E.assert_records_within(dn, n, a, got, gv, gu)
     # non-finite input (check_finite=False): NaN where the oracle has NaN, everything else equal
     got = n_(Q().eig_sym(F.t(R.vote_nonfinite(a)), check_finite=False))
     assert np.array_equal(np.isnan(got), np.isnan(ref_nf))
