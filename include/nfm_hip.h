@@ -585,6 +585,51 @@ int nfm_rt_transform_mm(int dtype, int kind, int type, int norm, int transpose, 
  * is not slower than the torch.fft composition in both layouts, 64 if neither (NFM_EDTYPE for an unknown dtype) */
 int nfm_rt_mm_max_len(int dtype);
 
+/* ------------------------------------------------------------- stochastic ---- */
+
+/* The library side of `stochastic.py` (`trapprox` :9-146, `maxeig_power` :316-362): the operator is the
+ * caller's, the probes, inner products, deflation and normalisation around it are these three kernels.
+ * Vectors are contiguous runs of n elements at element-aligned device pointers; at most
+ * NFM_STOCH_MAX_VECS of them per argument.  Pointer ARRAYS (`x`, `y`, `z`) live on the HOST and are copied
+ * into the kernel arguments, so a captured graph keeps them.  No atomics: every result has the same bits on
+ * every call, and the same bits whether or not the pointers are 16-byte aligned. */
+#define NFM_STOCH_MAX_VECS 8
+#define NFM_STOCH_RADEMACHER 0 /* +1 / -1 with probability 1/2 (`stochastic.py:84-88`) */
+#define NFM_STOCH_GAUSSIAN 1   /* standard normal (`stochastic.py:90-92`) */
+#define NFM_STOCH_SCALE_NONE 0          /* sigma = 1 */
+#define NFM_STOCH_SCALE_RSQRT 1         /* sigma = 1 / sqrt(*s) */
+#define NFM_STOCH_SCALE_RSQRT_OR_DROP 2 /* the same if *s > (64 eps_dtype)^2 * *s_ref and *s is finite and positive;
+                                           otherwise the output is zeroed */
+
+/* Philox4x32-10 on the host: counter[4], key[2] -> out[4].  The generator of nfm_stoch_fill, for known-answer tests. */
+int nfm_stoch_philox_host(const uint32_t *counter, const uint32_t *key, uint32_t *out);
+
+/* out[i] = probe element `offset + i`, i in [0, n).  Element e is a function of (seed, e) alone: the same bits
+ * whatever the launch geometry, the split of a range into several calls or the alignment of `out`.
+ * Key = (seed low word, seed high word).
+ * RADEMACHER: counter (e / 128 low, high, 0, 0); bit (e % 128) % 32 of word (e % 128) / 32: set = +1, clear = -1.
+ * GAUSSIAN:   counter (e / 4 low, high, 0, 1); words (w0, w1), (w2, w3) are two Box-Muller pairs with
+ *             u = (2 (w >> 9) + 1) 2^-24, r = sqrt(-2 ln u_a); elements 0..3 of the counter are
+ *             r0 cos, r0 sin, r1 cos, r1 sin of 2 pi u_b; evaluated in float for NFM_F32, in double for NFM_F64. */
+int nfm_stoch_fill(int dtype, int kind, uint64_t seed, int64_t offset, int64_t n, void *out, void *stream);
+
+/* bytes of device workspace nfm_stoch_gram needs for (p, q) (independent of n); 0 for p or q outside 1..8 */
+size_t nfm_stoch_gram_workspace_bytes(int p, int q);
+
+/* out[j q + k] (+)= sum_i X_j[i] Y_k[i], 1 <= p, q <= NFM_STOCH_MAX_VECS (the m^2 `dot`s of `outerpp`,
+ * `stochastic.py:111-116`, and every `flatten().dot()`).  Each X_j and Y_k is read once; products and sums in
+ * double.  `out`: p q doubles anywhere in device memory (8-byte aligned); `accumulate` != 0 adds to them.
+ * n == 0 sets them to 0 (or leaves them, with `accumulate`). */
+int nfm_stoch_gram(int dtype, int p, int q, int64_t n, const void *const *x, const void *const *y, void *workspace,
+                   size_t workspace_bytes, double *out, int accumulate, void *stream);
+
+/* Z_k = sigma (Y_k - sum_j X_j C[j q + k]), 0 <= p <= 8 (0: a pure scale; x and c may be NULL), 1 <= q <= 8
+ * (`mmpp`, `stochastic.py:118-123`, and `v /= dot(v, v).sqrt_()`, :359).  `c` (p q doubles), `s_ref` and `s` are
+ * DEVICE pointers; `scale_op` is one of NFM_STOCH_SCALE_*.  Arithmetic in double, one rounding on store.
+ * z[k] may be y[k] (in place); other overlaps are not allowed. */
+int nfm_stoch_combine(int dtype, int p, int q, int64_t n, const void *const *x, const double *c, const void *const *y,
+                      void *const *z, int scale_op, const double *s_ref, const double *s, void *stream);
+
 /* ------------------------------------------------------------------- misc ---- */
 
 const char *nfm_strerror(int code);

@@ -2,7 +2,8 @@
 small-matrix hot path of nitorch-fastmath: `sym`, `batched`, `qr`, the NaN-omitting
 reductions of `reduce`, the matrix exponential of `lie`, the matrix logarithm / exponential barycentre
 of `logm`, the implicit-class softmax family of `simplex`, the Bessel / digamma functions of `special` and the small solves of `sugar`
-(lmdiv / rmdiv / solvevec / inv), and the cosine / sine transforms of `realtransforms`,
+(lmdiv / rmdiv / solvevec / inv), the cosine / sine transforms of `realtransforms`, and the probes, inner products and
+orthogonalisation around the caller's operator in `stochastic` (trapprox / vbald / maxeig_power),
 behind the reference's own Python function signatures.
 
 Host code is Python on PyTorch-ROCm (device memory, streams); the arithmetic is
@@ -10,7 +11,7 @@ hand-written HIP in `libnfm_hip.so`, reached through the C ABI of include/nfm_hi
 There is no CPU path: importing works anywhere, calling needs the built library and
 GPU tensors.
 """
-from . import sym, batched, reduce, qr, lie, logm, simplex, special, sugar, realtransforms, utils  # noqa: F401
+from . import sym, batched, reduce, qr, lie, logm, simplex, special, sugar, realtransforms, stochastic, utils  # noqa: F401
 from .sym import *       # noqa: F401,F403
 from .batched import *   # noqa: F401,F403
 from .qr import *        # noqa: F401,F403

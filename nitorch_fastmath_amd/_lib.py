@@ -32,6 +32,10 @@ LSTSQ_MAX_ROWS, LSTSQ_MAX_N = 4096, 8    # include/nfm_hip.h: NFM_LSTSQ_MAX_ROWS
 RT_DCT, RT_DST = 0, 1
 RT_NORMS = {'backward': 0, 'forward': 1, 'ortho': 2, 'ortho_scipy': 3}
 SIDE = {'left': 0, 'right': 1, 'both': 2}
+# include/nfm_hip.h: NFM_STOCH_*
+STOCH_MAX_VECS = 8
+STOCH_RADEMACHER, STOCH_GAUSSIAN = 0, 1
+STOCH_SCALE_NONE, STOCH_SCALE_RSQRT, STOCH_SCALE_RSQRT_OR_DROP = 0, 1, 2
 
 
 class Operand(ctypes.Structure):
@@ -99,6 +103,11 @@ SIGNATURES = {
     'nfm_reduce_median': [_i, _i, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],
     'nfm_reduce_median_lane_max': [_i],
     'nfm_reduce_median_mid': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_stoch_philox_host': [_vp, _vp, _vp],
+    'nfm_stoch_fill': [_i, _i, ctypes.c_uint64, _i64, _i64, _vp, _vp],
+    'nfm_stoch_gram_workspace_bytes': [_i, _i],
+    'nfm_stoch_gram': [_i, _i, _i, _i64, _vp, _vp, _vp, ctypes.c_size_t, _vp, _i, _vp],
+    'nfm_stoch_combine': [_i, _i, _i, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     'nfm_qr_givens': [_i, _i64, _i64, _op, _op, _vp, _vp],
     'nfm_qr_givens_apply': [_i, _i, _i, _i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_qr_householder': [_i, _i, _i, _i64, _i64, _op, _vp, _vp],
