@@ -22,6 +22,9 @@
 //
 // LogmCore<T, D, true> carries the derivative of every value along (A', M', Y', Z', ...): the same steps
 // differentiated, with inv' = -Mi M' Mi.
+// Its roots end on another test: at the second step in a row whose M before the step had
+// ||M - I||_1 <= sqrt(eps).  M' lags M by a step, and where M - I is nilpotent (a unipotent A: a translation) M
+// reaches I exactly while M' is of order one.
 #pragma once
 #include "nfm_record_kernel.hpp"
 #include "nfm_smallmat.hpp"
@@ -245,11 +248,13 @@ struct LogmCore {
     {
         NFM_LOGM_NO_CONTRACT
         using E = LogmEps<T>;
-        const T theta = T(0.25), tol_m = T(4 * D) * E::eps;
+        [[maybe_unused]] const T tol_m = T(4 * D) * E::eps;
+        const T theta = T(0.25);
         bool bad = !logm_finite<T, D>(y);
         if constexpr (DUAL) bad = bad || !logm_finite<T, D>(yd);
         bool done = bad || logm_dist1<T, D>(y) <= theta;
         int s = 0, it = 0;
+        [[maybe_unused]] bool was_near = false; // the step before started within sqrt(eps) (this root)
         Mat m;
         [[maybe_unused]] Dual md;
 #pragma unroll
@@ -326,11 +331,19 @@ struct LogmCore {
                 for (int j = 0; j < D; ++j)
                     m[i][j] = T(0.5) * (T(i == j ? 1 : 0) + T(0.5) * (m[i][j] + mi[i][j]));
             ++it;
-            const bool conv = logm_dist1<T, D>(m) <= tol_m || e_prev <= E::sqrt_eps;
+            // With the derivative carried along, the root ends at the second step in a row that started within
+            // sqrt(eps): m can reach I, even exactly, while md is still of order one (a unipotent matrix:
+            // m - I is nilpotent and vanishes after a few steps), and y' needs the steps that consume that md.
+            // A step from ||m - I|| = e leaves md of order e md: the first of the two makes e rounding-sized,
+            // the second md.
+            const bool near = e_prev <= E::sqrt_eps;
+            const bool conv = DUAL ? near && was_near : logm_dist1<T, D>(m) <= tol_m || near;
+            was_near = near;
             if (conv) {
                 // this root is done: count it and start the next one on y (or leave)
                 ++s;
                 it = 0;
+                was_near = false;
                 done = logm_dist1<T, D>(y) <= theta || s >= kLogmMaxRoots;
 #pragma unroll
                 for (int i = 0; i < D; ++i)

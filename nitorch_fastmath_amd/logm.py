@@ -49,15 +49,16 @@ def _tree_sum(x):
 
 def _logm_torch(A):
     """The kernel's algorithm (Q20) in batched torch operations: the batch runs its largest number of square
-    roots, steps and series terms, each matrix its own under per-matrix masks.  Differentiable by autograd; same
-    NaN policy.  One host read per Denman-Beavers step (the loop ends when every matrix has converged) and one
-    for the largest degree.  The arithmetic of a matrix does not involve its batch mates, but the library routines
+    roots, steps and series terms, each matrix its own under per-matrix masks.  Differentiable by autograd (the
+    roots end on the Frechet kernel's stop test, which waits for the derivative of M as well); same NaN policy.
+    One host read per Denman-Beavers step (the loop ends when every matrix has converged) and one for the largest
+    degree.  The arithmetic of a matrix does not involve its batch mates, but the library routines
     behind `matmul` / `inv_ex` may pick other kernels for another batch size: bit-for-bit independence of the
     batch is a property of the HIP kernels' orders only."""
     D = _square(A)
     fi = torch.finfo(A.dtype)
     eye = torch.eye(D, dtype=A.dtype, device=A.device)
-    tol_m, sqrt_eps = 4 * D * fi.eps, fi.eps ** 0.5
+    sqrt_eps = fi.eps ** 0.5
 
     def sel(mask, a, b):
         return torch.where(mask[..., None, None], a, b)
@@ -72,6 +73,7 @@ def _logm_torch(A):
         M = sel(active, Y, eye)
         R = M
         conv = ~active
+        was_near = torch.zeros_like(conv)
         for _ in range(MAX_ITER):
             e_prev = _dist1(M.detach(), eye)
             Mi = torch.linalg.inv_ex(M).inverse
@@ -84,7 +86,12 @@ def _logm_torch(A):
             upd = upd & fin
             R = sel(upd, Rn, R)
             M = sel(upd, Mn, sel(bad, eye, M))
-            conv = conv | (upd & ((_dist1(M.detach(), eye) <= tol_m) | (e_prev <= sqrt_eps)))
+            # the stop test of the kernel that carries the derivative (autograd or jvp may be differentiating these
+            # steps): the second step in a row that started within sqrt(eps) ends the root, so that the derivative
+            # of M, which lags M by a step and is of order one where M reaches I at once (unipotent A), is consumed
+            near = e_prev <= sqrt_eps
+            conv = conv | (upd & near & was_near)
+            was_near = near
             if bool(conv.all()):
                 break
         bad = bad | ~conv
@@ -146,6 +153,12 @@ def logm(mat):
     Returns `(..., N, N)`, contiguous, in the input's dtype (Q21).  A matrix without a real principal
     logarithm gives NaN in every entry (Q22).  Differentiable: the backward is L_log(X^T, G), the Frechet
     kernel at orders 1..5 and autograd through the torch route above them.
+
+    Accuracy (Q20; m = max(1, cond_log(X)), cond_log = ||L_log(X)||_2 ||X||_F / ||log X||_F): the relative
+    Frobenius error is within 128 eps m for scales to 2^+-60, graded spectra, rotations up to pi - 0.1, unipotent
+    and triangular matrices; within 0.03 rad of pi it grows like eps cond_log^2, and a strongly non-normal matrix
+    (off-diagonals of 10..100 around a spectrum in [0.5, 2], rotated) may lose a few thousand eps m or come
+    back NaN.  kappa_1(X) does not bound the error.
     """
     from ._autograd import LogmFn
     _, _, (mat,) = prepare(None, mat, grad_ok=True)

@@ -128,6 +128,93 @@ def test_torch_route_on_the_fixture():
     assert torch.equal(_logm_torch(torch.eye(4).expand(3, 4, 4)), torch.zeros(3, 4, 4))
 
 
+def _hard_cases():
+    import _logm_ref as R
+    return [(dt, D) for dt in R.ORDERS for D in list(R.ORDERS[dt]) + list(R.ROUTE_ORDERS[dt])]
+
+
+def test_hard_fixture_invariants():
+    """tests/golden/logm_hard.npz: every truth validated at 1e-30, the classes and tiers as the generator states them,
+    every class of both tiers at every order with a kernel"""
+    import _logm_ref as R
+    g = R.load()
+    demoted = {tuple(s.split('/')[:3]) for s in g['demoted'].tolist()}
+    no_pair = set(g['no_pair'].tolist())
+    assert all(s.endswith('/rot') for s in no_pair)
+    for dt, D in _hard_cases():
+        rec = R.records(g, dt, D)
+        route = D in R.ROUTE_ORDERS[dt]
+        n = len(rec['x'])
+        assert rec['x'].dtype == (np.float32 if dt == 'f32' else np.float64) and rec['true'].dtype == np.float64
+        assert rec['x'].shape == rec['true'].shape == (n, D, D)
+        assert np.isfinite(rec['x']).all() and np.isfinite(rec['true']).all()
+        assert (rec['res'] <= 1e-30).all()
+        assert (rec['nK'] > 0).all() and (rec['cl'] > 0).all()
+        np.testing.assert_allclose(rec['cl'], rec['nK'] * R.fro(rec['x']) / R.fro(rec['true']), rtol=1e-12)
+        want = []
+        for cls, (tier, pars) in R.CLASSES.items():
+            if route and tier == R.TIER_B:
+                continue
+            k = 2 if route else R.PER_CLASS
+            tier = R.TIER_B if (dt, str(D), cls) in demoted else tier
+            name, p = 'rot' if cls == 'rotb' else cls, pars[dt]
+            want += [(name, tier, float(p[(i + D) % len(p)])) for i in range(k)]
+        assert list(zip(rec['cls'].tolist(), rec['tier'].tolist(), rec['par'].tolist())) == want, (dt, D)
+        if D in R.FRECHET_ORDERS:
+            assert rec['E'].shape == rec['L'].shape == (n, D, D) and np.isfinite(rec['L']).all()
+            # ||L_log(x, E)||_F <= ||K||_2 ||E||_F
+            assert (R.fro(rec['L']) <= rec['nK'] * R.fro(rec['E']) * (1 + 1e-6)).all()
+        if not route:
+            sm, sa, st = (g[f'{k}_{dt}_{D}'] for k in ('sm', 'sa', 'strue'))
+            # every tier-A class but those of which the generator found no M^-1 A with a real logarithm
+            ta = [c for c, (t, _) in R.CLASSES.items() if t == R.TIER_A and f'{dt}/{D}/{c}' not in no_pair]
+            assert g[f'scls_{dt}_{D}'].tolist() == ta and len(ta) >= 4
+            assert sm.shape == sa.shape == st.shape == (len(ta), D, D) and (g[f'sres_{dt}_{D}'] <= 1e-30).all()
+            np.testing.assert_allclose(g[f'skap_{dt}_{D}'], np.linalg.cond(sm.astype(np.float64), 1), rtol=1e-9)
+            assert g[f'skap_{dt}_{D}'].max() <= (1e4 if dt == 'f32' else 1e8) * 10
+
+
+def test_hard_fixture_truths_validate_again():
+    """one record of every class (float64, order 3) through mpmath again: the residual the generator recorded"""
+    import mpmath
+    import _logm_ref as R
+    g = R.load()
+    rec = R.records(g, 'f64', 3)
+    for i in range(0, len(rec['x']), R.PER_CLASS):
+        with mpmath.workdps(60):
+            A = R.mp_of(rec['x'][i])
+            L, res, _ = R.mp_logm(A)
+            assert L is not None and res <= 1e-30
+            assert np.abs(R.mp_to_np(L) - rec['true'][i]).max() <= 2.0 ** -50 * np.abs(rec['true'][i]).max()
+
+
+@pytest.mark.parametrize('dt,D', _hard_cases())
+def test_torch_route_on_the_hard_fixture(dt, D):
+    """`_logm_torch`, the kernel's algorithm, on the CPU over the whole hard fixture under the bounds the kernels are
+    held to (tests/_logm_ref.py): tier A without a NaN, tier B NaN or within eps m^2, the jvp, logm_solve"""
+    import _logm_ref as R
+    from torch.func import jvp
+    from nitorch_fastmath_amd.logm import _logm_torch
+    g = R.load()
+    rec = R.records(g, dt, D)
+    x = torch.from_numpy(rec['x'])
+    ok, r, what = R.check_logm(_logm_torch(x).numpy(), rec, dt)
+    print(dt, D, 'route worst err / (eps m):', {k: f'{v:.3g}' for k, v in R.worst_by_class(r, rec).items()})
+    assert ok.all(), [(rec['cls'][i], float(rec['par'][i]), what[i], float(r[i])) for i in np.flatnonzero(~ok)]
+    if D in R.FRECHET_ORDERS:
+        l = jvp(_logm_torch, (x,), (torch.from_numpy(rec['E']),))[1].numpy()
+        ta = rec['tier'] == R.TIER_A
+        rf = R.frechet_ratio(l, rec, dt)
+        print(dt, D, 'jvp worst err / (D eps m^2 ||K|| ||E||):',
+              {k: f'{v:.3g}' for k, v in R.worst_by_class(rf, rec).items()})
+        assert np.isfinite(l[ta]).all() and (rf[ta] <= R.C_LOGM).all(), rf
+    if D not in R.ROUTE_ORDERS[dt]:
+        sm, sa, st, kap, cl = (g[f'{k}_{dt}_{D}'] for k in ('sm', 'sa', 'strue', 'skap', 'scl'))
+        k = _logm_torch(torch.linalg.solve(torch.from_numpy(sm), torch.from_numpy(sa))).double().numpy()
+        rs = R.fro(k - st) / R.fro(st) / (D * R.EPS[dt] * kap * R.m_of(cl))
+        assert np.isfinite(k).all() and (rs <= R.C_LOGM).all(), rs
+
+
 def _census():
     import glob
     objs = sorted(glob.glob(os.path.join(ROOT, 'nitorch_fastmath_amd', 'csrc', 'nfm_logm.o')))
