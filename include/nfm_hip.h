@@ -285,6 +285,39 @@ int nfm_reduce_median_lane_max(int dtype);
 int nfm_reduce_median_mid(int dtype, int omitnan, int64_t outer, int64_t red, int64_t inner, const void *x, void *val,
                           void *idx, void *stream);
 
+/* Quantiles of every row of a contiguous (rows, red) array: the median's radix selection at several
+ * arbitrary ranks per row.  The reference has no counterpart (its one order statistic is `median`,
+ * `reduce.py:384-428`); the conventions are the median's: keys ordered -0.0 before +0.0 and NaN last,
+ * omitnan = 0: a NaN in a row makes every quantile of the row NaN, omitnan = 1: the quantiles of the
+ * non-NaN elements (all NaN: NaN).  With count = the elements counted, p = fl64(q * (count - 1)),
+ * lo = floor(p), hi = ceil(p), w = p - lo and v_lo, v_hi the order statistics of those ranks:
+ * NFM_QUANTILE_LOWER v_lo; HIGHER v_hi; NEAREST the rank rint(p), half to even; MIDPOINT = LINEAR with
+ * w = 0.5; LINEAR v_lo when v_lo == v_hi (no arithmetic: two equal infinities give that infinity), else in
+ * float64 w < 0.5 ? a + w (b - a) : b - (b - a) (1 - w), rounded once to `dtype`.
+ * q: nq numbers in [0, 1] on the HOST, read during the call and passed to the kernels by value (nothing is
+ * copied to the device: the call can be captured in a graph).  val: (nq, rows) of `dtype`.  pos: NULL or
+ * (nq, rows, 2) int64 = the first position in the row holding v_lo and the first holding v_hi (LOWER,
+ * HIGHER, NEAREST: twice the position of the chosen element; a NaN result: 0, 0).
+ * Rows of more than 1024 elements need a workspace of nfm_reduce_quantile_workspace_bytes(rows, red, nq)
+ * bytes (0 for shorter rows; it grows with nq) and rows <= 65535.
+ * Checks, before any HIP call, in this precedence: dtype (NFM_EDTYPE); rows < 0, red < 0, nq < 1, a bad
+ * interp (NFM_EINVAL); nq > nfm_reduce_quantile_max_q() (NFM_ESIZE); q NULL, a q outside [0, 1] or NaN
+ * (NFM_EINVAL); rows == 0: NFM_OK without a launch; red == 0, x or val NULL (NFM_EINVAL); red > 1024:
+ * rows > 65535 (NFM_ESIZE), then a workspace that is NULL or too small (NFM_EINVAL, as nfm_reduce_median).
+ * nfm_reduce_quantile_plan_host runs the kernels' own rank routine on the CPU: the ranks the selection
+ * resolves (LOWER / HIGHER / NEAREST: lo == hi == the chosen rank, w = 0; MIDPOINT: w = 0.5) for count >= 1
+ * (count == 0, a bad q or interp, a NULL output: NFM_EINVAL). */
+#define NFM_QUANTILE_LINEAR 0
+#define NFM_QUANTILE_LOWER 1
+#define NFM_QUANTILE_HIGHER 2
+#define NFM_QUANTILE_NEAREST 3
+#define NFM_QUANTILE_MIDPOINT 4
+int nfm_reduce_quantile_max_q(void); /* quantiles one launch takes (8) */
+size_t nfm_reduce_quantile_workspace_bytes(int64_t rows, int64_t red, int nq);
+int nfm_reduce_quantile(int dtype, int omitnan, int interp, int64_t rows, int64_t red, int nq, const double *q,
+                        const void *x, void *workspace, size_t workspace_bytes, void *val, void *pos, void *stream);
+int nfm_reduce_quantile_plan_host(double q, uint64_t count, int interp, uint64_t *lo, uint64_t *hi, double *w);
+
 /* ------------------------------------------------------------------- qr ---- */
 /* Real dtypes.  Multi-output routines write ONE packed, contiguous output record per
  * matrix into `out` (n_outer * n_inner records, batch-major); the layout of the record

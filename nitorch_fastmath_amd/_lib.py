@@ -32,6 +32,8 @@ LSTSQ_MAX_ROWS, LSTSQ_MAX_N = 4096, 8    # include/nfm_hip.h: NFM_LSTSQ_MAX_ROWS
 RT_DCT, RT_DST = 0, 1
 RT_NORMS = {'backward': 0, 'forward': 1, 'ortho': 2, 'ortho_scipy': 3}
 SIDE = {'left': 0, 'right': 1, 'both': 2}
+# include/nfm_hip.h: NFM_QUANTILE_*
+QUANTILE_INTERP = {'linear': 0, 'lower': 1, 'higher': 2, 'nearest': 3, 'midpoint': 4}
 # include/nfm_hip.h: NFM_STOCH_*
 STOCH_MAX_VECS = 8
 STOCH_RADEMACHER, STOCH_GAUSSIAN = 0, 1
@@ -103,6 +105,11 @@ SIGNATURES = {
     'nfm_reduce_median': [_i, _i, _i64, _i64, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],
     'nfm_reduce_median_lane_max': [_i],
     'nfm_reduce_median_mid': [_i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_reduce_quantile_max_q': [],
+    'nfm_reduce_quantile_workspace_bytes': [_i64, _i64, _i],
+    'nfm_reduce_quantile': [_i, _i, _i, _i64, _i64, _i, _dp, _vp, _vp, ctypes.c_size_t, _vp, _vp, _vp],
+    'nfm_reduce_quantile_plan_host': [ctypes.c_double, ctypes.c_uint64, _i, ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.POINTER(ctypes.c_uint64), _dp],
     'nfm_stoch_philox_host': [_vp, _vp, _vp],
     'nfm_stoch_fill': [_i, _i, ctypes.c_uint64, _i64, _i64, _vp, _vp],
     'nfm_stoch_gram_workspace_bytes': [_i, _i],

@@ -21,10 +21,12 @@ flag is accepted and the input is left bit-identical (pinned by
 tests/test_gpu_reduce.py::test_inplace_never_modifies_the_input, recorded in INTEGRATION.md).
 '''
 __all__ = [
-    'min', 'max', 'nanmin', 'nanmax', 'median',
+    'min', 'max', 'nanmin', 'nanmax', 'median', 'quantile', 'nanquantile',
     'sum', 'nansum', 'mean', 'nanmean', 'var', 'nanvar', 'std', 'nanstd'
 ]
 import builtins
+import ctypes
+import numbers
 import torch
 from . import _lib
 from ._dispatch import call, dtype_code, needs_grad, no_grad_required, require_gpu
@@ -356,6 +358,156 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
         if scalar_dim:
             sub = sub[..., 0]
     return val, _deliver(sub, out_ind)
+
+
+# Long rows (more than 1024 elements) are selected over HBM and need 16 KiB of 64-bit histogram bins per row AND
+# per quantile of the launch: the rows of one call are split so that its workspace stays within this budget
+# (the median's step of 16384 rows would be 2 GiB at 8 quantiles).  64 MiB = 510 rows at 8 quantiles.
+_QUANTILE_WS_BUDGET = 64 << 20
+
+
+def _quantile_q(q):
+    """`q` -> (list of Python floats, is it a scalar).  `q` lives on the host: a device tensor is copied there
+    (a synchronisation -- pass Python numbers to avoid it)."""
+    if isinstance(q, torch.Tensor):
+        if q.dim() > 1:
+            raise ValueError(f'quantile: q must be a number or 1-d, got a {q.dim()}-d tensor')
+        scalar = q.dim() == 0
+        qs = q.detach().to('cpu', torch.float64).reshape(-1).tolist()
+    elif isinstance(q, numbers.Real):
+        scalar, qs = True, [float(q)]
+    else:
+        scalar, qs = False, [float(v) for v in q]
+    if not qs:
+        raise ValueError('quantile: q is empty')
+    for v in qs:
+        if not 0.0 <= v <= 1.0:           # (false for a NaN)
+            raise ValueError(f'quantile: q must lie in [0, 1], got {v}')
+    return qs, scalar
+
+
+def _quantile_call(dev, code, omitnan, interp, x, qb, val, pos):
+    """one `nfm_reduce_quantile` call: x (rows, red) contiguous, len(qb) <= the cap, val (len(qb), rows)
+    contiguous, pos None or (len(qb), rows, 2)"""
+    L = _lib.lib()
+    rows, red = x.shape
+    ws, wsn = _workspace(dev, L.nfm_reduce_quantile_workspace_bytes(rows, red, len(qb)))
+    call(L.nfm_reduce_quantile, dev, code, int(bool(omitnan)), interp, rows, red, len(qb),
+         (ctypes.c_double * len(qb))(*qb), x.data_ptr(), ws.data_ptr() if ws is not None else None, wsn,
+         val.data_ptr(), pos.data_ptr() if pos is not None else None)
+
+
+def _quantile_rows(dev, code, omitnan, interp, x, qs, val, pos):
+    """all of `qs` on the rows of x: blocks of q at the cap of one launch, blocks of rows at the workspace budget"""
+    L = _lib.lib()
+    rows, red = x.shape
+    cap = L.nfm_reduce_quantile_max_q()
+    for q0 in range(0, len(qs), cap):
+        qb = qs[q0:q0 + cap]
+        per_row = L.nfm_reduce_quantile_workspace_bytes(1, red, len(qb))
+        step = rows if per_row == 0 else builtins.max(1, builtins.min(65535, _QUANTILE_WS_BUDGET // per_row))
+        if step >= rows:
+            _quantile_call(dev, code, omitnan, interp, x, qb, val[q0:q0 + len(qb)],
+                           pos[q0:q0 + len(qb)] if pos is not None else None)
+            continue
+        for lo in range(0, rows, step):       # the kernel writes (q, rows of the block): through a temporary
+            hi = builtins.min(rows, lo + step)
+            v = torch.empty((len(qb), hi - lo), dtype=val.dtype, device=dev)
+            p = torch.empty((len(qb), hi - lo, 2), dtype=torch.long, device=dev) if pos is not None else None
+            _quantile_call(dev, code, omitnan, interp, x[lo:hi], qb, v, p)
+            val[q0:q0 + len(qb), lo:hi] = v
+            if pos is not None:
+                pos[q0:q0 + len(qb), lo:hi] = p
+
+
+def quantile(input, q, dim=None, keepdim=False, omitnan=False, inplace=False, interpolation='linear', out=None):
+    r"""Multi-dimensional quantiles by the radix selection of `median`, at several ranks per pass over the data
+    (`nfm_reduce_quantile`).  The reference has no such function; the conventions are this module's, not
+    `torch.quantile`'s: `dim` may be None, an int or a list of dims; `inplace` is accepted and the input is never
+    written; GPU tensors of float32 / float64 only.  No sort, no limit on the input size.
+
+    q : a Python number, or a sequence / 1-d tensor of numbers, in [0, 1] (outside, NaN or empty: ValueError).
+        q lives on the HOST: a device tensor is copied there, which synchronises.  A scalar q gives the reduced
+        shape, a 1-d q of length Q gives (Q, \*reduced shape), like `torch.quantile`.
+
+    Definition, per reduced slice ("row"):
+      - count = its elements (`omitnan`: its non-NaN elements).  With `omitnan=False` a NaN anywhere in the row
+        makes every quantile of the row NaN; count == 0 gives NaN.
+      - p = fl64(q * (count - 1)) -- one double multiplication; lo = floor(p), hi = ceil(p), w = p - lo;
+        v_lo, v_hi = the order statistics of those ranks, ascending, keys ordered as `median` orders them
+        (-0.0 before +0.0, NaN last).
+      - 'lower': v_lo; 'higher': v_hi; 'nearest': the order statistic of rank rint(p), half to even (as numpy
+        and torch); 'midpoint': 'linear' with w = 0.5;
+      - 'linear': v_lo if v_lo == v_hi -- no arithmetic, so two equal infinities give that infinity (numpy and
+        torch return NaN there) -- else, in float64, `a + w (b - a)` if w < 0.5 else `b - (b - a) (1 - w)`,
+        rounded once to the input dtype (IEEE rules when one of the two is infinite; float64 inputs whose
+        difference overflows are not rescaled).
+      - a reduced dim of size 0 raises IndexError, like `median`.
+
+    With a gradient: the kernel also returns the first positions holding v_lo and v_hi, the two values are
+    gathered from the differentiable rows and combined by the same formula in torch ops, so the gradient is
+    (1 - w, w) on the two selected elements; among tied elements it goes to the FIRST position holding the value.
+    `out=` with a gradient raises RuntimeError.
+    """
+    input = torch.as_tensor(input)
+    dev = require_gpu(input)
+    grad = needs_grad(input)
+    if grad and out is not None:
+        raise RuntimeError('out= is not supported for tensors that require grad')
+    code = dtype_code(input.dtype)
+    if interpolation not in _lib.QUANTILE_INTERP:
+        raise ValueError(f'quantile: interpolation must be one of {sorted(_lib.QUANTILE_INTERP)}, got {interpolation!r}')
+    interp = _lib.QUANTILE_INTERP[interpolation]
+    qs, scalar_q = _quantile_q(q)
+    nd = input.dim()
+    dims = list(range(nd)) if dim is None else [d if d >= 0 else nd + d for d in ensure_list(dim)]
+    if len(set(dims)) != len(dims) or any(d < 0 or d >= nd for d in dims):
+        raise IndexError(f'invalid reduction dims {dim} for a {nd}-d tensor')
+    kept = [d for d in range(nd) if d not in dims]
+    subshape = [input.shape[d] for d in kept]
+    red, rows = _prod([input.shape[d] for d in dims]), _prod(subshape)
+    if red == 0:
+        raise IndexError('cannot take a quantile over an empty dimension')
+    xg = input.permute(kept + dims).reshape(rows, red)   # differentiable view / copy of the rows
+    x = xg.detach()
+    if not x.is_contiguous():
+        x = x.contiguous()
+    val = torch.empty((len(qs), rows), dtype=input.dtype, device=dev)
+    pos = torch.empty((len(qs), rows, 2), dtype=torch.long, device=dev) if grad else None
+    _quantile_rows(dev, code, omitnan, interp, x, qs, val, pos)
+    if grad:
+        val = _quantile_with_grad(xg, x, qs, omitnan, interpolation, val, pos)
+    shape = [1 if d in dims else s for d, s in enumerate(input.shape)] if keepdim else subshape
+    val = val.reshape(shape) if scalar_q else val.reshape([len(qs)] + shape)
+    return _deliver(val, out)
+
+
+def _quantile_with_grad(xg, x, qs, omitnan, interpolation, val, pos):
+    """the kernel's result rebuilt from the differentiable rows: gather v_lo and v_hi at the positions the kernel
+    found, combine them as the kernel does (float64, the same formula); NaN results carry no gradient"""
+    nq, rows = val.shape
+    red = x.shape[1]
+    picked = xg.gather(1, pos.permute(1, 0, 2).reshape(rows, 2 * nq)).reshape(rows, nq, 2)
+    a, b = picked[..., 0].t(), picked[..., 1].t()                   # (nq, rows)
+    if interpolation in ('linear', 'midpoint'):
+        if interpolation == 'midpoint':
+            w = torch.full((nq, rows), 0.5, dtype=torch.float64, device=x.device)
+        else:
+            count = (red - torch.isnan(x).sum(1)) if omitnan else torch.full((rows,), red, device=x.device)
+            p = torch.tensor(qs, dtype=torch.float64, device=x.device)[:, None] * (count - 1).clamp(min=0).to(torch.float64)
+            w = p - p.floor()
+        a64, b64 = a.to(torch.float64), b.to(torch.float64)
+        d = b64 - a64
+        r = torch.where(w < 0.5, a64 + w * d, b64 - d * (1 - w))
+        r = torch.where(a64 == b64, a64, r).to(val.dtype)
+    else:
+        r = a
+    return torch.where(torch.isnan(val), val, r)
+
+
+def nanquantile(input, q, dim=None, keepdim=False, inplace=False, interpolation='linear', out=None):
+    r"""`quantile` of the non-NaN values of every slice (`omitnan=True`); an all-NaN slice gives NaN."""
+    return quantile(input, q, dim, keepdim, True, inplace, interpolation, out)
 
 
 def sum(input, dim=None, keepdim=False, omitnan=False, inplace=False, dtype=None, out=None):
