@@ -26,64 +26,16 @@
 //                a trip over HBM, so the digits are 11 bits wide (2048 bins, 8 KiB of LDS): 3 passes
 //                for float32 (11 + 11 + 10 bits), 6 for float64 -- a full reduction of 2^33
 //                elements is 3 passes at the streaming rate.
+//
+// The counting rule, above(), the chunk walk and digit pick of the long rows and the launch ladders are in
+// nfm_reduce_select.hpp, shared with nfm_reduce_quantile.hip.
 #include "nfm_reduce_select.hpp"
 
 namespace nfm {
 namespace med {
 
-__device__ __forceinline__ unsigned wave_excl_scan(unsigned v, unsigned &total)
-{
-    const int lane = threadIdx.x & 63;
-    unsigned s = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned o = __shfl_up(s, off, 64);
-        if (lane >= off) s += o;
-    }
-    total = __shfl(s, 63, 64);
-    return s - v;
-}
-
-// pick the digit whose cumulative count passes k: `cnt` = this lane's 4 consecutive bins
-// (4 * lane .. 4 * lane + 3); returns the digit and reduces k to the rank inside that digit
-__device__ __forceinline__ unsigned pick_digit(const unsigned (&cnt)[4], unsigned long long &k)
-{
-    const int lane = threadIdx.x & 63;
-    unsigned tot;
-    const unsigned mine = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-    const unsigned before = wave_excl_scan(mine, tot);
-    const bool here = (unsigned long long)before <= k && k < (unsigned long long)before + mine;
-    const unsigned long long m = __ballot(here);
-    const int src = m ? __builtin_ctzll(m) : 63; // k < total always: exactly one lane
-    unsigned digit = 0;
-    unsigned long long kk = k;
-    if (lane == src) {
-        unsigned long long r = k - before;
-        unsigned d = 0;
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-            if (d == (unsigned)b && r >= cnt[b]) {
-                r -= cnt[b];
-                d = b + 1;
-            }
-        digit = 4 * lane + d;
-        kk = r;
-    }
-    digit = __shfl(digit, src, 64);
-    const unsigned lo = __shfl((unsigned)kk, src, 64), hi = __shfl((unsigned)(kk >> 32), src, 64);
-    k = ((unsigned long long)hi << 32) | lo;
-    return digit;
-}
-
 // ---------------------------------------------------------------------------------------------
 // short rows: one wavefront per 1 / 2 / 4 rows
-// the part of a key above digit d (0 for the top digit: nothing chosen yet)
-template <typename U>
-__device__ __forceinline__ U above(U key, int d, int digits)
-{
-    return d + 1 < digits ? (U)(key >> (8 * (d + 1))) : U(0);
-}
-
 // G lanes per row (16 / 32 / 64: 4 / 2 / 1 rows per wavefront), E keys per lane: rows of up to G * E
 // elements.  The per-pass frame (clear the histogram, scan it, pick the digit) is the same instruction
 // stream whatever the row length, so short rows share a wavefront: 4 rows of <= 256 elements cost what
@@ -116,8 +68,7 @@ __global__ __launch_bounds__(256) void median_rows_kernel(const T *__restrict__ 
     }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) nan += __shfl_xor(nan, off, G);
-    const unsigned count = omitnan ? (unsigned)red - nan : (unsigned)red;
-    const bool want_nan = (!omitnan && nan > 0) || count == 0;
+    const auto [count, want_nan] = row_count((unsigned)red, nan, omitnan);
     unsigned k = count ? (count - 1) / 2 : 0;
     U prefix = 0;
 #pragma unroll
@@ -210,8 +161,7 @@ __global__ __launch_bounds__(256) void median_tiny_kernel(const T *__restrict__ 
     unsigned nan = (live && v != v) ? 1u : 0u;
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) nan += __shfl_xor(nan, off, 64);
-    const unsigned count = omitnan ? (unsigned)red - nan : (unsigned)red;
-    const bool want_nan = (!omitnan && nan > 0) || count == 0;
+    const auto [count, want_nan] = row_count((unsigned)red, nan, omitnan);
     const unsigned k = count ? (count - 1) / 2 : 0;
     unsigned rank = 0;
     for (int t = 0; t < red; ++t) { // red is uniform; positions beyond it hold nothing
@@ -263,8 +213,6 @@ __global__ __launch_bounds__(256) void median_hist_kernel(const T *__restrict__ 
     using K = Key<T>;
     using U = typename K::U;
     using D = LongDigits<T>;
-    using V = typename VecOf<T>::gtype;
-    constexpr int NV = VecOf<T>::N;
     __shared__ unsigned hist[kLongBins];
     __shared__ unsigned nan_s;
     const int64_t row = blockIdx.y;
@@ -278,27 +226,13 @@ __global__ __launch_bounds__(256) void median_hist_kernel(const T *__restrict__ 
     const int shift = D::shift(pass), width = D::width(pass);
     const int up = first_pass ? 0 : shift + width; // bits above this digit: chosen already (never the full width)
     const unsigned mask = (1u << width) - 1u;
-    const T *p = x + row * red;
     const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < red ? lo + chunk : red;
     unsigned nan = 0;
-    auto take = [&](T v) {
+    stream_chunk<T>(x + row * red, lo, hi, [&](T v, int64_t) __attribute__((always_inline)) {
         const U key = K::of(v);
         if (first_pass) nan += (v != v) ? 1u : 0u;
         if (first_pass || (U)(key >> up) == prefix) atomicAdd(&hist[(unsigned)(key >> shift) & mask], 1u);
-    };
-    // 16-byte loads over the aligned middle of the chunk, elements at its ragged ends
-    int64_t j = lo + threadIdx.x;
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(p + lo) / sizeof(T)) % NV);
-    const int64_t head = mis ? (NV - mis < hi - lo ? NV - mis : hi - lo) : 0;
-    if (j < lo + head) take(NFM_LDG(p + j));
-    const int64_t body0 = lo + head, nvec = (hi - body0) / NV;
-    for (int64_t q = threadIdx.x; q < nvec; q += 256) {
-        const V v = NFM_LDG(reinterpret_cast<const V *>(p + body0) + q);
-#pragma unroll
-        for (int c = 0; c < NV; ++c) take(v[c]);
-    }
-    j = body0 + nvec * NV + threadIdx.x;
-    if (j < hi) take(NFM_LDG(p + j));
+    });
     if (first_pass) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) nan += __shfl_xor(nan, off, 64);
@@ -329,8 +263,8 @@ __global__ __launch_bounds__(64) void median_pick_kernel(int64_t red, int pass, 
     if (pass == 0) {
         s.prefix = 0;
         s.nan = gnan[row];
-        const unsigned long long count = omitnan ? (unsigned long long)red - s.nan : (unsigned long long)red;
-        s.want_nan = ((!omitnan && s.nan > 0) || count == 0) ? 1 : 0;
+        const auto [count, want_nan] = row_count((ull)red, s.nan, omitnan);
+        s.want_nan = want_nan ? 1 : 0;
         s.k = count ? (count - 1) / 2 : 0;
         s.first = red; // "not found yet" for the index pass
     }
@@ -372,8 +306,7 @@ __global__ __launch_bounds__(256) void median_index_kernel(const T *__restrict__
         }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo32 = __shfl_xor((unsigned)first, off, 64), hi32 = __shfl_xor((unsigned)(first >> 32), off, 64);
-        const unsigned long long o = ((unsigned long long)hi32 << 32) | lo32;
+        const unsigned long long o = __shfl_xor(first, off, 64);
         first = o < first ? o : first;
     }
     if ((threadIdx.x & 63) == 0 && first != ~0ull) atomicMin(&st[row].first, first);
@@ -436,36 +369,16 @@ static int run(int omitnan, int64_t rows, int64_t red, const void *x, void *ws, 
     if (red > LaneMax<T>::value && red <= 2 * LaneMax<T>::value && rows >= kLanePadMinRows &&
         reinterpret_cast<uintptr_t>(x) % sizeof(T) == 0)
         return lane_pad_any<T>((int)red, omitnan, rows, x, val, idx, stream);
-    if (red <= 32) {
-        const int G = red <= 8 ? 8 : (red <= 16 ? 16 : 32);
-        const int64_t nblk = (rows + 4 * (64 / G) - 1) / (4 * (64 / G));
-        if (nblk > 0x7fffffffLL) return NFM_ESIZE;
-#define NFM_MED_TINY(Gv)                                                                                              \
-    hipLaunchKernelGGL((median_tiny_kernel<T, Gv>), dim3((unsigned)nblk), dim3(256), 0, s, static_cast<const T *>(x), \
-                       rows, (int)red, omitnan, static_cast<T *>(val), static_cast<int64_t *>(idx))
-        if (G == 8) NFM_MED_TINY(8);
-        else if (G == 16) NFM_MED_TINY(16);
-        else NFM_MED_TINY(32);
-#undef NFM_MED_TINY
-        return launch_status();
-    }
-    if (red <= kShortMax) {
-#define NFM_MED_ROWS(Ev, Gv)                                                                                          \
-    {                                                                                                                 \
-        const int64_t nblk = (rows + 4 * (64 / Gv) - 1) / (4 * (64 / Gv));                                            \
-        if (nblk > 0x7fffffffLL) return NFM_ESIZE;                                                                    \
-        hipLaunchKernelGGL((median_rows_kernel<T, Ev, Gv>), dim3((unsigned)nblk), dim3(256), 0, s,                    \
-                           static_cast<const T *>(x), rows, (int)red, omitnan, static_cast<T *>(val),                 \
-                           static_cast<int64_t *>(idx));                                                              \
-    }
-        if (red <= 64) NFM_MED_ROWS(4, 16)
-        else if (red <= 128) NFM_MED_ROWS(8, 16)
-        else if (red <= 256) NFM_MED_ROWS(16, 16)
-        else if (red <= 512) NFM_MED_ROWS(16, 32)
-        else NFM_MED_ROWS(16, 64)
-#undef NFM_MED_ROWS
-        return launch_status();
-    }
+    if (red <= 32)
+        return launch_tiny(rows, red, [&](auto, auto g, unsigned nblk) {
+            hipLaunchKernelGGL((median_tiny_kernel<T, g()>), dim3(nblk), dim3(256), 0, s, static_cast<const T *>(x), rows,
+                               (int)red, omitnan, static_cast<T *>(val), static_cast<int64_t *>(idx));
+        });
+    if (red <= kShortMax)
+        return launch_rows(rows, red, [&](auto e, auto g, unsigned nblk) {
+            hipLaunchKernelGGL((median_rows_kernel<T, e(), g()>), dim3(nblk), dim3(256), 0, s, static_cast<const T *>(x),
+                               rows, (int)red, omitnan, static_cast<T *>(val), static_cast<int64_t *>(idx));
+        });
     if (rows > 65535) return NFM_ESIZE; // grid.y; the facade splits (long rows are few)
     const size_t need = (size_t)rows * (sizeof(RowState) + kLongBins * sizeof(unsigned long long) + sizeof(unsigned long long));
     if (ws == nullptr || ws_bytes < need) return NFM_EINVAL;

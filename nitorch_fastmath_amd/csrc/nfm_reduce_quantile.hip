@@ -23,15 +23,27 @@
 //                successor pass then collects per state #(keys <= key_lo), the smallest key above key_lo and,
 //                when positions are wanted, the first position of key_lo (a further pass finds the first
 //                position of key_hi: only the autograd route asks for it).
+//
+// Shared with the median through nfm_reduce_select.hpp: above(), the chunk walk, the digit pick, the counting rule
+// (where it leaves a kernel's code as it was) and the launch ladders.  The two register forms above and the
+// first-pass histogram repeat the text of the median's kernels: built from common blocks they were scheduled
+// differently and measurably slower (profiles/select_refactor.md).
 #include "nfm_reduce_select.hpp"
 
 namespace nfm {
 namespace qnt {
 
+// the selection building blocks (nfm_reduce_select.hpp)
+using med::above;
 using med::Key;
 using med::kLongBins;
+using med::launch_rows;
+using med::launch_tiny;
 using med::LongDigits;
-using ull = unsigned long long;
+using med::pick_digit_n;
+using med::row_count;
+using med::stream_chunk;
+using med::ull;
 
 constexpr int kMaxQ = 8; // rank states of one launch: 8 x 8 KiB of LDS histograms
 struct QArgs {
@@ -90,25 +102,6 @@ __device__ __forceinline__ T combine(typename Key<T>::U klo, typename Key<T>::U 
     return (T)r;
 }
 
-template <typename U>
-__device__ __forceinline__ U shfl_key(U key, int src)
-{
-    if constexpr (sizeof(U) == 4) return (U)__shfl((unsigned)key, src, 64);
-    else {
-        const unsigned lo = __shfl((unsigned)key, src, 64), hi = __shfl((unsigned)(key >> 32), src, 64);
-        return ((U)hi << 32) | lo;
-    }
-}
-template <typename U>
-__device__ __forceinline__ U shfl_xor_key(U key, int off, int width)
-{
-    if constexpr (sizeof(U) == 4) return (U)__shfl_xor((unsigned)key, off, width);
-    else {
-        const unsigned lo = __shfl_xor((unsigned)key, off, width), hi = __shfl_xor((unsigned)(key >> 32), off, width);
-        return ((U)hi << 32) | lo;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
 // tiny rows (red <= 32): G lanes per row, one element per lane, the rank of every element counted directly
 template <typename T, int G>
@@ -127,11 +120,12 @@ __global__ __launch_bounds__(256) void quantile_tiny_kernel(const T *__restrict_
     unsigned nan = (live && v != v) ? 1u : 0u;
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) nan += __shfl_xor(nan, off, 64);
+    // (the rule of row_count, written out: through it this kernel's code is scheduled differently)
     const unsigned count = omitnan ? (unsigned)red - nan : (unsigned)red;
     const bool want_nan = (!omitnan && nan > 0) || count == 0;
     unsigned rank = 0;
     for (int t = 0; t < red; ++t) { // red is uniform; positions beyond it hold nothing
-        const U kt = shfl_key(key, gbase + t);
+        const U kt = __shfl(key, gbase + t, 64);
         rank += (kt < key || (kt == key && t < j)) ? 1u : 0u;
     }
     const ull gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << gbase;
@@ -140,8 +134,8 @@ __global__ __launch_bounds__(256) void quantile_tiny_kernel(const T *__restrict_
         // exactly one live lane of the row holds each rank below count (NaN keys are the largest)
         const ull hit_lo = __ballot(live && rank == (unsigned)pl.lo) & gmask;
         const ull hit_hi = __ballot(live && rank == (unsigned)pl.hi) & gmask;
-        const U klo = shfl_key(key, hit_lo ? __builtin_ctzll(hit_lo) : gbase);
-        const U khi = shfl_key(key, hit_hi ? __builtin_ctzll(hit_hi) : gbase);
+        const U klo = __shfl(key, hit_lo ? __builtin_ctzll(hit_lo) : gbase, 64);
+        const U khi = __shfl(key, hit_hi ? __builtin_ctzll(hit_hi) : gbase, 64);
         const ull same_lo = __ballot(live && key == klo) & gmask;
         const ull same_hi = __ballot(live && key == khi) & gmask;
         if (j == 0 && row < rows) {
@@ -158,12 +152,6 @@ __global__ __launch_bounds__(256) void quantile_tiny_kernel(const T *__restrict_
 // ---------------------------------------------------------------------------------------------
 // short rows (red <= 1024): G lanes per row, E keys per lane (median_rows_kernel); the row is read once,
 // the digit loop runs once per q on the keys in registers
-template <typename U>
-__device__ __forceinline__ U above(U key, int d, int digits)
-{
-    return d + 1 < digits ? (U)(key >> (8 * (d + 1))) : U(0);
-}
-
 template <typename T, int E, int G>
 __global__ __launch_bounds__(256) void quantile_rows_kernel(const T *__restrict__ x, int64_t rows, int red, int omitnan,
                                                             int interp, int nq, QArgs qa, T *__restrict__ val,
@@ -193,8 +181,7 @@ __global__ __launch_bounds__(256) void quantile_rows_kernel(const T *__restrict_
     }
 #pragma unroll
     for (int off = G / 2; off > 0; off >>= 1) nan += __shfl_xor(nan, off, G);
-    const unsigned count = omitnan ? (unsigned)red - nan : (unsigned)red;
-    const bool want_nan = (!omitnan && nan > 0) || count == 0;
+    const auto [count, want_nan] = row_count((unsigned)red, nan, omitnan);
     for (int s = 0; s < nq; ++s) {
         // what derives from the keys alone (the digits of every pass) stays inside the loop: hoisted out of it,
         // those values cost three times the registers of median_rows_kernel and half its wavefronts per SIMD
@@ -268,7 +255,7 @@ __global__ __launch_bounds__(256) void quantile_rows_kernel(const T *__restrict_
 #pragma unroll
         for (int off = G / 2; off > 0; off >>= 1) {
             cle += __shfl_xor(cle, off, G);
-            const U o = shfl_xor_key(succ, off, G);
+            const U o = __shfl_xor(succ, off, G);
             succ = o < succ ? o : succ;
         }
         const U khi = (pl.hi == pl.lo || (ull)cle > pl.lo + 1) ? klo : succ;
@@ -319,27 +306,6 @@ static_assert(sizeof(QRow) == 16 && sizeof(QState) == 48, "workspace layout");
 static size_t workspace_need(int64_t rows, int nq)
 {
     return (size_t)rows * (sizeof(QRow) + (size_t)nq * (sizeof(QState) + kLongBins * sizeof(ull)));
-}
-
-// walk the chunk [lo, hi) of the row: 16-byte loads over the aligned middle, elements at its ragged ends;
-// f(value, position in the row)
-template <typename T, typename F>
-__device__ __forceinline__ void stream_chunk(const T *__restrict__ p, int64_t lo, int64_t hi, F &&f)
-{
-    using V = typename VecOf<T>::gtype;
-    constexpr int NV = VecOf<T>::N;
-    int64_t j = lo + threadIdx.x;
-    const int64_t mis = (int64_t)((reinterpret_cast<uintptr_t>(p + lo) / sizeof(T)) % NV);
-    const int64_t head = mis ? (NV - mis < hi - lo ? NV - mis : hi - lo) : 0;
-    if (j < lo + head) f(NFM_LDG(p + j), j);
-    const int64_t body0 = lo + head, nvec = (hi - body0) / NV;
-    for (int64_t q = threadIdx.x; q < nvec; q += 256) {
-        const V v = NFM_LDG(reinterpret_cast<const V *>(p + body0) + q);
-#pragma unroll
-        for (int c = 0; c < NV; ++c) f(v[c], body0 + q * NV + c);
-    }
-    j = body0 + nvec * NV + threadIdx.x;
-    if (j < hi) f(NFM_LDG(p + j), j);
 }
 
 // first pass: no prefix yet, so every rank state reads the same histogram (that of state 0); counts the NaNs
@@ -430,9 +396,9 @@ __global__ __launch_bounds__(64) void quantile_pick_kernel(int64_t red, int pass
     const int64_t row = blockIdx.x;
     const int lane = threadIdx.x;
     QRow r = ri[row];
-    const ull count = omitnan ? (ull)red - r.nan : (ull)red;
+    const auto [count, want_nan] = row_count((ull)red, r.nan, omitnan);
     if (pass == 0) {
-        r.want_nan = ((!omitnan && r.nan > 0) || count == 0) ? 1 : 0;
+        r.want_nan = want_nan ? 1 : 0;
         if (lane == 0) ri[row].want_nan = r.want_nan;
     }
     if (r.want_nan) return; // no later pass touches the row
@@ -462,7 +428,7 @@ __global__ __launch_bounds__(64) void quantile_pick_kernel(int64_t red, int pass
             }
         }
         ull k = qs.k;
-        const unsigned digit = med::pick_digit_n<NB>(cnt, k);
+        const unsigned digit = pick_digit_n<NB>(cnt, k);
         qs.k = k;
         qs.prefix = (qs.prefix << D::width(pass)) | digit;
         if (lane == 0) st[row * nq + s] = qs;
@@ -514,7 +480,7 @@ __global__ __launch_bounds__(256) void quantile_succ_kernel(const T *__restrict_
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) {
                     c += __shfl_xor(c, off, 64);
-                    const U o = shfl_xor_key(m, off, 64);
+                    const U o = __shfl_xor(m, off, 64);
                     m = o < m ? o : m;
                 }
                 if ((threadIdx.x & 63) == 0) {
@@ -526,7 +492,7 @@ __global__ __launch_bounds__(256) void quantile_succ_kernel(const T *__restrict_
                 ull f = first[s];
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) {
-                    const ull o = shfl_xor_key(f, off, 64);
+                    const ull o = __shfl_xor(f, off, 64);
                     f = o < f ? o : f;
                 }
                 if ((threadIdx.x & 63) == 0 && f != ~0ull) atomicMin(which ? &q->first_hi : &q->first_lo, f);
@@ -544,7 +510,7 @@ __global__ void quantile_resolve_kernel(int64_t rows, int64_t red, int omitnan, 
     const int64_t row = i / nq;
     const int s = (int)(i - row * nq);
     if (ri[row].want_nan) return;
-    const ull count = omitnan ? (ull)red - ri[row].nan : (ull)red;
+    const ull count = omitnan ? (ull)red - ri[row].nan : (ull)red; // (row_count; the NaN count is loaded only when omitted)
     const Plan pl = plan_of(q_at(qa, s), count, interp);
     QState q = st[i];
     st[i].succ = (pl.hi == pl.lo || q.cnt_le > pl.lo + 1) ? q.prefix : q.succ;
@@ -567,7 +533,7 @@ __global__ void quantile_final_kernel(int64_t rows, int64_t red, int omitnan, in
         if (pos) pos[2 * o] = pos[2 * o + 1] = 0;
         return;
     }
-    const ull count = omitnan ? (ull)red - ri[row].nan : (ull)red;
+    const ull count = omitnan ? (ull)red - ri[row].nan : (ull)red; // (row_count; the NaN count is loaded only when omitted)
     const Plan pl = plan_of(q_at(qa, s), count, interp);
     const QState q = st[i];
     const U klo = (U)q.prefix, khi = have_hi ? (U)q.succ : klo;
@@ -587,35 +553,16 @@ static int run(int omitnan, int interp, int64_t rows, int64_t red, int nq, const
     const T *xp = static_cast<const T *>(x);
     T *vp = static_cast<T *>(val);
     int64_t *pp = static_cast<int64_t *>(pos);
-    if (red <= 32) {
-        const int G = red <= 8 ? 8 : (red <= 16 ? 16 : 32);
-        const int64_t nblk = (rows + 4 * (64 / G) - 1) / (4 * (64 / G));
-        if (nblk > 0x7fffffffLL) return NFM_ESIZE;
-#define NFM_QNT_TINY(Gv)                                                                                               \
-    hipLaunchKernelGGL((quantile_tiny_kernel<T, Gv>), dim3((unsigned)nblk), dim3(256), 0, s, xp, rows, (int)red, omitnan, \
-                       interp, nq, qa, vp, pp)
-        if (G == 8) NFM_QNT_TINY(8);
-        else if (G == 16) NFM_QNT_TINY(16);
-        else NFM_QNT_TINY(32);
-#undef NFM_QNT_TINY
-        return launch_status();
-    }
-    if (red <= med::kShortMax) {
-#define NFM_QNT_ROWS(Ev, Gv)                                                                                           \
-    {                                                                                                                  \
-        const int64_t nblk = (rows + 4 * (64 / Gv) - 1) / (4 * (64 / Gv));                                             \
-        if (nblk > 0x7fffffffLL) return NFM_ESIZE;                                                                     \
-        hipLaunchKernelGGL((quantile_rows_kernel<T, Ev, Gv>), dim3((unsigned)nblk), dim3(256), 0, s, xp, rows, (int)red, \
-                           omitnan, interp, nq, qa, vp, pp);                                                           \
-    }
-        if (red <= 64) NFM_QNT_ROWS(4, 16)
-        else if (red <= 128) NFM_QNT_ROWS(8, 16)
-        else if (red <= 256) NFM_QNT_ROWS(16, 16)
-        else if (red <= 512) NFM_QNT_ROWS(16, 32)
-        else NFM_QNT_ROWS(16, 64)
-#undef NFM_QNT_ROWS
-        return launch_status();
-    }
+    if (red <= 32)
+        return launch_tiny(rows, red, [&](auto, auto g, unsigned nblk) {
+            hipLaunchKernelGGL((quantile_tiny_kernel<T, g()>), dim3(nblk), dim3(256), 0, s, xp, rows, (int)red, omitnan,
+                               interp, nq, qa, vp, pp);
+        });
+    if (red <= med::kShortMax)
+        return launch_rows(rows, red, [&](auto e, auto g, unsigned nblk) {
+            hipLaunchKernelGGL((quantile_rows_kernel<T, e(), g()>), dim3(nblk), dim3(256), 0, s, xp, rows, (int)red,
+                               omitnan, interp, nq, qa, vp, pp);
+        });
     if (rows > 65535) return NFM_ESIZE; // grid.y; the facade splits (long rows are few)
     const size_t need = workspace_need(rows, nq);
     if (ws == nullptr || ws_bytes < need) return NFM_EINVAL;

@@ -272,6 +272,21 @@ def nanmin(input, dim=None, keepdim=False, inplace=False, return_indices=False, 
     return min(input, dim, keepdim, True, inplace, return_indices, out)
 
 
+def _select_rows(input, dim, keepdim):
+    """The slices `median` / `quantile` select from, as rows: (dims, redshape, red, rows, result shape, rows_view).
+    `rows_view()` makes the differentiable (rows, red) view / copy on demand: `median`'s middle-dim route needs none."""
+    nd = input.dim()
+    dims = list(range(nd)) if dim is None else [d if d >= 0 else nd + d for d in ensure_list(dim)]
+    if len(set(dims)) != len(dims) or any(d < 0 or d >= nd for d in dims):
+        raise IndexError(f'invalid reduction dims {dim} for a {nd}-d tensor')
+    kept = [d for d in range(nd) if d not in dims]
+    redshape = [input.shape[d] for d in dims]
+    subshape = [input.shape[d] for d in kept]
+    red, rows = _prod(redshape), _prod(subshape)
+    shape = [1 if d in dims else s for d, s in enumerate(input.shape)] if keepdim else subshape
+    return dims, redshape, red, rows, shape, lambda: input.permute(kept + dims).reshape(rows, red)
+
+
 def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_indices=False, out=None):
     r"""Multi-dimensional median (`reduce.py:384-428`): the lower of the two middle values for an
     even count, and the index of the first element that holds it.
@@ -292,7 +307,6 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
     if grad and out is not None:
         raise RuntimeError('out= is not supported for tensors that require grad')
     code = dtype_code(input.dtype)
-    nd = input.dim()
     if not grad and out is None and isinstance(dim, int) and not input.is_contiguous():
         # a dim permutation of a contiguous tensor (the channel-last VIEW of a channel-first field):
         # reduce the corresponding dim of the contiguous tensor in place instead of copying the view
@@ -304,13 +318,7 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
                 return _uncanon(r[0], inv, odims, keepdim), _uncanon(r[1], inv, odims, keepdim)
             return _uncanon(r, inv, odims, keepdim)
     scalar_dim = dim is not None and not isinstance(dim, (list, tuple, range))
-    dims = list(range(nd)) if dim is None else [d if d >= 0 else nd + d for d in ensure_list(dim)]
-    if len(set(dims)) != len(dims) or any(d < 0 or d >= nd for d in dims):
-        raise IndexError(f'invalid reduction dims {dim} for a {nd}-d tensor')
-    kept = [d for d in range(nd) if d not in dims]
-    redshape = [input.shape[d] for d in dims]
-    subshape = [input.shape[d] for d in kept]
-    red, rows = _prod(redshape), _prod(subshape)
+    dims, redshape, red, rows, shape, rows_view = _select_rows(input, dim, keepdim)
     if red == 0:
         raise IndexError('cannot take the median over an empty dimension')
     val = torch.empty(rows, dtype=input.dtype, device=dev)
@@ -331,7 +339,7 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
         rows_done = False
     x = None
     if grad or not rows_done:
-        xg = input.permute(kept + dims).reshape(rows, red)   # differentiable view / copy of the rows
+        xg = rows_view()
     if not rows_done:
         x = xg.detach()
         if not x.is_contiguous():
@@ -345,7 +353,6 @@ def median(input, dim=None, keepdim=False, omitnan=False, inplace=False, return_
              idx[lo:hi].data_ptr() if idx is not None else None)
     if grad:      # the gradient goes to the selected element: pick it out of the differentiable rows
         val = xg.gather(1, idx[:, None])[:, 0]
-    shape = [1 if d in dims else s for d, s in enumerate(input.shape)] if keepdim else subshape
     val = val.reshape(shape)
     out_val, out_ind = ensure_list(out, 2, default=None) if out is not None else (None, None)
     val = _deliver(val, out_val)
@@ -459,16 +466,10 @@ def quantile(input, q, dim=None, keepdim=False, omitnan=False, inplace=False, in
         raise ValueError(f'quantile: interpolation must be one of {sorted(_lib.QUANTILE_INTERP)}, got {interpolation!r}')
     interp = _lib.QUANTILE_INTERP[interpolation]
     qs, scalar_q = _quantile_q(q)
-    nd = input.dim()
-    dims = list(range(nd)) if dim is None else [d if d >= 0 else nd + d for d in ensure_list(dim)]
-    if len(set(dims)) != len(dims) or any(d < 0 or d >= nd for d in dims):
-        raise IndexError(f'invalid reduction dims {dim} for a {nd}-d tensor')
-    kept = [d for d in range(nd) if d not in dims]
-    subshape = [input.shape[d] for d in kept]
-    red, rows = _prod([input.shape[d] for d in dims]), _prod(subshape)
+    _, _, red, rows, shape, rows_view = _select_rows(input, dim, keepdim)
     if red == 0:
         raise IndexError('cannot take a quantile over an empty dimension')
-    xg = input.permute(kept + dims).reshape(rows, red)   # differentiable view / copy of the rows
+    xg = rows_view()
     x = xg.detach()
     if not x.is_contiguous():
         x = x.contiguous()
@@ -477,7 +478,6 @@ def quantile(input, q, dim=None, keepdim=False, omitnan=False, inplace=False, in
     _quantile_rows(dev, code, omitnan, interp, x, qs, val, pos)
     if grad:
         val = _quantile_with_grad(xg, x, qs, omitnan, interpolation, val, pos)
-    shape = [1 if d in dims else s for d, s in enumerate(input.shape)] if keepdim else subshape
     val = val.reshape(shape) if scalar_q else val.reshape([len(qs)] + shape)
     return _deliver(val, out)
 

@@ -469,6 +469,31 @@ def test_median_vs_oracle_and_torch(dev, oracle, dn, red):
 
 
 @pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_median_indices_misaligned_base(dev, oracle, dn):
+    """values AND indices from rows whose base pointer sits one element off a 16-byte line (the flat buffer from
+    1 on, as test_gpu_quantile.on_gpu makes it): 4 and 2 rows per wavefront with a ragged last wavefront, and long
+    rows, whose chunk walk then has a ragged head and tail around its 16-byte loads.  Duplicates, a row with one
+    NaN, an all-NaN row; equal to the oracle's, bit for bit"""
+    dtype = np.float32 if dn == 'f32' else np.float64
+    for rows, red in ((5, 33), (17, 257), (3, 1025), (2, 16385)):
+        rng = np.random.default_rng(rows * red)
+        x = (np.round(rng.standard_normal((rows, red)) * 4) / 4).astype(dtype)      # many duplicates
+        x[0, red // 3] = np.nan
+        x[-1] = np.nan                                                              # all NaN
+        flat = torch.empty(x.size + 1, dtype=torch.from_numpy(x).dtype, device=dev)
+        xd = flat[1:].view(x.shape)
+        xd.copy_(torch.from_numpy(x))
+        assert xd.is_contiguous() and xd.data_ptr() % 16 != 0
+        for omit in (False, True):
+            v, i = R().median(xd, dim=1, omitnan=omit, return_indices=True)
+            rv, ri = oracle.median(x, 1, omitnan=omit)
+            v, i = v.cpu().numpy(), i.cpu().numpy()
+            assert np.array_equal(np.isnan(v), np.isnan(rv)), (rows, red, omit)
+            assert np.array_equal(v[~np.isnan(v)].view(np.uint8), rv[~np.isnan(rv)].view(np.uint8)), (rows, red, omit)
+            assert np.array_equal(i, ri), (rows, red, omit)
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
 def test_median_row_per_lane(dev, oracle, dn):
     """rows of 2..128 (float64: 2..64) elements in batches of >= 4096 rows: one row per lane, sorted in registers by
     the merge-exchange network (median_lane_kernel) -- every length, ragged last tile, NaNs (kept and
