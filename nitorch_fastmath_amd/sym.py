@@ -24,6 +24,8 @@ __all__ = [
     'sym_solve', 'sym_solve_',
     'sym_invert', 'sym_invert_',
     'sym_matmul_solve',      # extension: fused Gauss-Newton step (not in the reference)
+    # extensions: spectral functions of compact symmetric matrices (not in the reference)
+    'sym_funm', 'sym_expm', 'sym_logm', 'sym_sqrtm', 'sym_rsqrtm', 'sym_powm', 'sym_clampm',
 ]
 import ctypes
 from math import sqrt
@@ -434,3 +436,139 @@ def sym_matmul_solve(j, h, g, eps=None, dtype=None, out=None):
               [2, 1, 1, 1])
     launch(_lib.lib().nfm_sym_matmul_solve, dev, dtype, (k, d, hk), b, tail=(_eps_array(eps, d),))
     return out
+
+
+# ---------------------------------------------------------------- spectral functions (extension)
+_FUNM_CAPS = {}
+
+
+def _funm_cap(dtype, backward):
+    """largest order with a kernel: the compiled table of the library (`nfm_sym_funm_max_order`)"""
+    key = (dtype, bool(backward))
+    if key not in _FUNM_CAPS:
+        from ._dispatch import dtype_code
+        _FUNM_CAPS[key] = int(_lib.lib().nfm_sym_funm_max_order(dtype_code(dtype), int(bool(backward))))
+    return _FUNM_CAPS[key]
+
+
+def _funm_args(fn, p, min):
+    from math import isfinite
+    if fn not in _lib.FUN:
+        raise ValueError(f"fn must be one of {sorted(_lib.FUN)}, got {fn!r}")
+    if fn == 'pow':
+        if p is None:
+            raise ValueError("fn='pow' needs the exponent p")
+        p = float(p)
+        if not isfinite(p):
+            raise ValueError('p must be finite')
+    else:
+        p = 0.0
+    if min is None:
+        if fn == 'clamp':
+            raise ValueError("fn='clamp' needs min")
+    else:
+        min = float(min)
+        if not isfinite(min):
+            raise ValueError('min must be finite')
+    return _lib.FUN[fn], p, min
+
+
+def _deliver(res, out):
+    if out is None:
+        return res
+    if tuple(out.shape) != tuple(res.shape) or out.dtype != res.dtype or out.device != res.device:
+        raise ValueError('out must have the shape, the computation dtype and the device of the result')
+    return out.copy_(res)
+
+
+def _funm_forward(mat, code, p, vmin, dtype, out):
+    dev, dtype, (mat,) = prepare(dtype, mat)
+    M = _nb_prm(mat.shape[-1])
+    if M > _funm_cap(dtype, False):          # no kernel at this order: torch.linalg.eigh on the device (_symfun.py)
+        from . import _symfun
+        return _deliver(_symfun.forward(mat, code, p, vmin), out)
+    batch = mat.shape[:-1]
+    out, _ = _alloc_out(out, tuple(mat.shape), dtype, dev, like=mat)
+    b = Batch(batch, [mat, out], [1, 1])
+    launch(_lib.lib().nfm_sym_funm, dev, dtype, (M, code, p, int(vmin is not None), 0.0 if vmin is None else vmin), b)
+    return out
+
+
+def _funm_backward(mat, gout, code, p, vmin, dtype):
+    dev, dtype, (mat, gout) = prepare(dtype, mat, gout)
+    M = _nb_prm(mat.shape[-1])
+    if M > _funm_cap(dtype, True):
+        from . import _symfun
+        return _symfun.backward(mat, gout, code, p, vmin)
+    batch = mat.shape[:-1]
+    gmat, _ = _alloc_out(None, tuple(mat.shape), dtype, dev, like=mat)
+    b = Batch(batch, [mat, expand_batch(batch, gout, 1), gmat], [1, 1, 1])
+    launch(_lib.lib().nfm_sym_funm_backward, dev, dtype,
+           (M, code, p, int(vmin is not None), 0.0 if vmin is None else vmin), b)
+    return gmat
+
+
+def sym_funm(mat, fn, p=None, min=None, dtype=None, out=None):
+    r"""EXTENSION (not in the reference): `f(A)` of compact symmetric matrices, compact in and compact out.
+
+    `A = V diag(l) V^T` per matrix, in the registers of one lane (the fast arithmetic of `qr.eig_sym`); the result is
+    `V diag(f(max(l, min))) V^T`.  One read of the `K = M(M+1)/2` values and one write, instead of
+    `sym_to_full` -> `eig_sym(compute_u=True)` -> dense products -> repack.
+
+    Parameters
+    ----------
+    mat : `(..., M*(M+1)//2) tensor`
+    fn : {'exp', 'log', 'sqrt', 'rsqrt', 'pow', 'clamp'}
+    p : `float`, the exponent of 'pow' (required there, ignored otherwise)
+    min : `float`, optional (required by 'clamp')
+        The eigenvalues are replaced by `max(l, min)` before `f`: `sym_clampm` is the projection onto
+        `{A >= min I}`, and `sym_logm(x, min=1e-6)` a safe logarithm of a nearly singular field.
+    dtype, out : as `sym_det`; `out=mat` (in place) is allowed.
+
+    Domains, judged after the clamp: 'exp' and 'clamp' take any eigenvalue; 'log', 'rsqrt' and 'pow' with `p < 0`
+    need `l > 0`; 'sqrt' and 'pow' with `p >= 0` need `l >= 0`.  A matrix with an eigenvalue outside the domain, or
+    with an entry that is not finite, gives NaN in every component of its result and of its gradient; its neighbours
+    are untouched.  No exception, no host synchronisation: a call (forward and backward) can be captured in a graph.
+
+    Differentiable once with respect to `mat`.  The gradient is the Daleckii-Krein form
+    `V [(V^T G V) o F] V^T` with closed-form divided differences `F`, regular at repeated and clustered
+    eigenvalues, in the compact convention of the module (what autograd gives for `pack(f(sym_to_full(x)))`).
+    Orders above the compiled caps (8; 7 for the float64 gradient) run `torch.linalg.eigh` on the device.
+    """
+    code, p, vmin = _funm_args(fn, p, min)
+    _nb_prm(torch.as_tensor(mat).shape[-1])
+    if needs_grad(mat):
+        _grad_guard(out)
+        from ._autograd import SymFunmFn
+        return SymFunmFn.apply(torch.as_tensor(mat), code, p, vmin, dtype)
+    return _funm_forward(mat, code, p, vmin, dtype, out)
+
+
+def sym_expm(mat, min=None, dtype=None, out=None):
+    """EXTENSION: matrix exponential of compact symmetric matrices (`sym_funm(mat, 'exp')`)."""
+    return sym_funm(mat, 'exp', min=min, dtype=dtype, out=out)
+
+
+def sym_logm(mat, min=None, dtype=None, out=None):
+    """EXTENSION: matrix logarithm of compact SPD matrices (`sym_funm(mat, 'log')`)."""
+    return sym_funm(mat, 'log', min=min, dtype=dtype, out=out)
+
+
+def sym_sqrtm(mat, min=None, dtype=None, out=None):
+    """EXTENSION: `A^(1/2)` of compact positive semi-definite matrices (`sym_funm(mat, 'sqrt')`)."""
+    return sym_funm(mat, 'sqrt', min=min, dtype=dtype, out=out)
+
+
+def sym_rsqrtm(mat, min=None, dtype=None, out=None):
+    """EXTENSION: `A^(-1/2)` of compact SPD matrices (`sym_funm(mat, 'rsqrt')`)."""
+    return sym_funm(mat, 'rsqrt', min=min, dtype=dtype, out=out)
+
+
+def sym_powm(mat, p, min=None, dtype=None, out=None):
+    """EXTENSION: `A^p` of compact positive (semi-)definite matrices (`sym_funm(mat, 'pow', p)`)."""
+    return sym_funm(mat, 'pow', p=p, min=min, dtype=dtype, out=out)
+
+
+def sym_clampm(mat, min, dtype=None, out=None):
+    """EXTENSION: projection onto `{A >= min I}`: the eigenvalues clamped from below (`sym_funm(mat, 'clamp')`)."""
+    return sym_funm(mat, 'clamp', min=min, dtype=dtype, out=out)
