@@ -201,6 +201,46 @@ int nfm_batch_matvec(int dtype, int rows, int cols, int64_t n_outer, int64_t n_i
                      const nfm_operand *a, const nfm_operand *v, const nfm_operand *out,
                      void *stream);
 
+/* EXTENSION (no counterpart in the reference): singular value and polar decompositions of general N x N matrices,
+ * one record per lane: the one-sided Jacobi sweeps of nfm_svd_solve (prescale by a power of two, relative rotation
+ * test, null guard, at most NFM_SVD_MAX_SWEEPS sweeps) on the rows of [a | I], a sort by descending singular value,
+ * and for rank-deficient records an orthonormal completion of the right singular vectors.
+ *   nfm_batch_svdvals: out record S (N), non-negative, descending.
+ *   nfm_batch_svd:     out record [S (N) | U (N x N) | Vh (N x N)], row-major blocks of one packed record of
+ *                      N + 2 N^2 values, a = U diag(S) Vh; U and Vh are orthogonal for every finite record.
+ *   nfm_batch_polar:   out record [R (N x N) | P (N x N)], a = R P, R = U Vh orthogonal, P = Vh^T diag(S) Vh with
+ *                      exactly equal mirrored entries.  For a singular record P is unique and R is one valid factor.
+ *   nfm_batch_polar_backward: ga = the gradient with respect to a given the cotangents gr of R and gp of P (either may
+ *                      be NULL, meaning zeros; not both).  The decomposition is recomputed from a.  With
+ *                      B = U^T gr V and C = V^T sym(gp) V: ga = U X V^T, X_ij = ((B - B^T)_ij + 2 s_i C_ij) / (s_i + s_j):
+ *                      finite at repeated singular values.  A record with two numerically null singular values
+ *                      (R is not differentiable there) and a non-zero gr is NaN; its gp part is finite.
+ * The out / gr / gp / ga operands describe their packed record with stride_col (stride_row is ignored for the
+ * packed outputs of the three forward entries; gr, gp and ga are N x N operands like a).  A record with an entry
+ * that is not finite gives a NaN record and nothing else.  N in 1..nfm_polar_max_order(dtype, op).
+ * Status precedence: NFM_EDTYPE; NFM_EINVAL negative count; NFM_ESIZE n_outer; NFM_ESIZE N outside 1..NFM_MAX_DIM;
+ * NFM_ESIZE N above the compiled cap (the caller's own route: the Python facade runs torch.linalg.svd there);
+ * NFM_EINVAL gr and gp both NULL; then the operands in argument order. */
+#define NFM_POLAR_OP_SVDVALS 0
+#define NFM_POLAR_OP_SVD 1
+#define NFM_POLAR_OP_POLAR 2
+#define NFM_POLAR_OP_POLAR_BACKWARD 3
+int nfm_batch_svdvals(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *a,
+                      const nfm_operand *out, void *stream);
+int nfm_batch_svd(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *a, const nfm_operand *out,
+                  void *stream);
+int nfm_batch_polar(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *a,
+                    const nfm_operand *out, void *stream);
+int nfm_batch_polar_backward(int dtype, int N, int64_t n_outer, int64_t n_inner, const nfm_operand *a,
+                             const nfm_operand *gr, const nfm_operand *gp, const nfm_operand *ga, void *stream);
+/* largest N with a kernel for op (NFM_POLAR_OP_*); 0 for an unknown dtype or op */
+int nfm_polar_max_order(int dtype, int op);
+/* CPU: the record routine of the kernels on n contiguous row-major host records (a: n x N x N; out as the entry
+ * of op writes it, packed; gr / gp only for NFM_POLAR_OP_POLAR_BACKWARD, either may be NULL).  N in
+ * 1..NFM_SVD_MAX_DIM whatever the compiled caps.  Returns the largest number of sweeps a record took (>= 0), or
+ * NFM_EDTYPE, NFM_EINVAL (n < 0, unknown op, a null pointer with n > 0, no cotangent), NFM_ESIZE. */
+int nfm_polar_host(int dtype, int op, int N, int64_t n, const void *a, const void *gr, const void *gp, void *out);
+
 /* ------------------------------------------------------------------ lie ---- */
 
 /* out = expm(x) for (D x D) matrices, `expm` / `expm_derivatives` without derivatives

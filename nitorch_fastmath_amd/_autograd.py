@@ -5,7 +5,7 @@ the backward of the reductions (mask, broadcast, divide) is plain torch on the d
 
 Covered: sym_matvec / sym_addmatvec / sym_submatvec, sym_solve, sym_invert (+ diag), sym_det,
 sym_to_full, sym_outer, sym_matmul,
-batchmatvec / batchinv / batchdet, eig_sym (eigenvalues, and eigenvectors through Giles' formula,
+batchmatvec / batchinv / batchdet, batchsvdvals / batchpolar, eig_sym (eigenvalues, and eigenvectors through Giles' formula,
 as upstream's `_EigSym` `_impl/qr.py:684-735` intends), sum / nansum / mean / nanmean,
 max / min / nanmax / nanmin (the cotangent goes to the selected element), var / std / nanvar /
 nanstd, expm, logm, the simplex functions softmax / log_softmax / logsumexp (one saved tensor each) and the special
@@ -257,6 +257,46 @@ class BatchInvFn(torch.autograd.Function):
         (inv,) = ctx.saved_tensors
         it = inv.transpose(-1, -2)
         return -_small_matmul(_small_matmul(it, g), it), None
+
+
+class BatchSvdvalsFn(torch.autograd.Function):
+    """S = svdvals(A):  dA = U diag(g) Vh.  Nothing but `a` is saved: the backward pass runs the SVD kernel."""
+
+    @staticmethod
+    def forward(ctx, a):
+        from . import batched as B
+        ctx.save_for_backward(a)
+        with torch.no_grad():
+            return B._svdvals(a)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import batched as B
+        (a,) = ctx.saved_tensors
+        U, _, Vh = B._svd(a)
+        return _small_matmul(U * g.unsqueeze(-2), Vh)
+
+
+class BatchPolarFn(torch.autograd.Function):
+    """(R, P) = polar(A).  Nothing but `a` is saved: one backward kernel recomputes the decomposition and applies
+    dA = U X V^T, X_ij = ((B - B^T)_ij + 2 s_i C_ij) / (s_i + s_j), B = U^T gR V, C = V^T sym(gP) V -- regular at
+    repeated singular values, unlike the 1 / (s_i^2 - s_j^2) of torch.linalg.svd's backward."""
+
+    @staticmethod
+    def forward(ctx, a):
+        from . import batched as B
+        ctx.save_for_backward(a)
+        ctx.set_materialize_grads(False)
+        with torch.no_grad():
+            return B._polar_forward(a)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gr, gp):
+        from . import batched as B
+        (a,) = ctx.saved_tensors
+        return B._polar_backward(a, None if gr is None else gr.to(a.dtype), None if gp is None else gp.to(a.dtype))
 
 
 class LmdivFn(torch.autograd.Function):

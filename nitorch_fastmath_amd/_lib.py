@@ -29,6 +29,7 @@ SP_MAX_N = 8
 SOLVE_LU, SOLVE_CHOL, SOLVE_MAX_DIM = 0, 1, 8    # include/nfm_hip.h: NFM_SOLVE_*
 ROWSOLVE_MIN_DIM = 9                             # include/nfm_hip.h: NFM_ROWSOLVE_MIN_DIM; nfm_rowsolve serves 9..MAX_DIM
 SVD_PLAIN, SVD_PINV, SVD_MAX_DIM, SVD_MAX_SWEEPS = 0, 1, 8, 16    # include/nfm_hip.h: NFM_SVD_*
+POLAR_SVDVALS, POLAR_SVD, POLAR_POLAR, POLAR_POLAR_BACKWARD = range(4)    # include/nfm_hip.h: NFM_POLAR_OP_*
 LSTSQ_MAX_ROWS, LSTSQ_MAX_N = 4096, 8    # include/nfm_hip.h: NFM_LSTSQ_MAX_ROWS, the N of nfm_lstsq_solve
 # include/nfm_hip.h: NFM_RT_*
 RT_DCT, RT_DST = 0, 1
@@ -75,6 +76,13 @@ SIGNATURES = {
     'nfm_batch_inv': [_i, _i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_det': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],
+    # (plain pointers for the same reason as nfm_sym_funm above; tests/test_polar_host.py makes the canonical bad calls)
+    'nfm_batch_svdvals': [_i, _i, _i64, _i64, _vp, _vp, _vp],
+    'nfm_batch_svd': [_i, _i, _i64, _i64, _vp, _vp, _vp],
+    'nfm_batch_polar': [_i, _i, _i64, _i64, _vp, _vp, _vp],
+    'nfm_batch_polar_backward': [_i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_polar_max_order': [_i, _i],
+    'nfm_polar_host': [_i, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_lie_expm': [_i, _i, _i, ctypes.c_double, _i64, _i64, _op, _op, _vp],
     'nfm_lie_expm_frechet': [_i, _i, _i, ctypes.c_double, _i64, _i64, _op, _op, _op, _op, _vp],
     'nfm_lie_logm': [_i, _i, _i64, _i64, _op, _op, _vp],
