@@ -177,6 +177,46 @@ int nfm_sym_funm_max_order(int dtype, int backward);
 int nfm_sym_funm_host_eval(int dtype, int fn, double p, int has_min, double vmin, int n, const void *lam, void *f,
                            void *dd);
 
+/* EXTENSION (no counterpart in the reference): spectral kernels of a pencil (base, mat) of compact symmetric
+ * matrices, base positive definite: with base = V L V^T, W = V L^-1/2, W^T mat W = Q M Q^T, X = W Q and Z = X^-T, both
+ * decompositions in the lane's registers (the arithmetic of nfm_sym_funm), every record read once.
+ * nfm_sym_pencil_funm: out = base^1/2 f(base^-1/2 mat base^-1/2) base^1/2 = Z f(M) Z^T, fn in NFM_FUN_EXP ..
+ * NFM_FUN_POW (POW with exponent t: the point base #_t mat of the geodesic; LOG / EXP: the Riemannian log / exp map at
+ * base); NFM_FUN_CLAMP and has_min != 0 are NFM_EINVAL.  `out` may be either input.
+ * nfm_sym_pencil_funm_backward: gmat = the gradient with respect to `mat` for the cotangent gout of the compact
+ * result, X [(Z^T G Z) o F] X^T, in the compact convention of nfm_sym_funm_backward.
+ * nfm_sym_pencil_eig: mode NFM_PENCIL_EIG: the M generalised eigenvalues of mat x = mu base x, ascending;
+ * NFM_PENCIL_DIST2: sum_i log^2 mu_i, the squared affine-invariant distance (one value); NFM_PENCIL_DIST: its root.
+ * nfm_sym_pencil_dist_backward: mode NFM_PENCIL_DIST2 or NFM_PENCIL_DIST; gout = the cotangent of that value (one per
+ * record); grads = records of 2 M (M + 1) / 2 values: the compact gradient with respect to base, then the one with
+ * respect to mat, -c X diag(2 log mu) X^T and c X diag(2 log mu / mu) X^T (exact and zero at base == mat); for
+ * NFM_PENCIL_DIST c = gout / (2 d), defined as 0 at d == 0 (a subgradient).
+ * A record with an entry of base or mat that is not finite, a computed eigenvalue of base that is not positive, or
+ * a mu outside the domain of f (the distance: mu <= 0) is NaN in every component; the other records do not notice.
+ * M in 1..nfm_sym_pencil_max_order(dtype, op).  Status precedence: that of nfm_sym_funm (NFM_EINVAL for an unknown
+ * fn or mode before NFM_ESIZE for M above the compiled cap, then NFM_EINVAL for p not finite, then the operands in
+ * argument order). */
+#define NFM_PENCIL_OP_FUNM 0
+#define NFM_PENCIL_OP_FUNM_BACKWARD 1
+#define NFM_PENCIL_OP_EIG 2
+#define NFM_PENCIL_OP_DIST_BACKWARD 3
+#define NFM_PENCIL_EIG 0
+#define NFM_PENCIL_DIST2 1
+#define NFM_PENCIL_DIST 2
+int nfm_sym_pencil_funm(int dtype, int M, int fn, double p, int has_min, double vmin, int64_t n_outer,
+                        int64_t n_inner, const nfm_operand *base, const nfm_operand *mat, const nfm_operand *out,
+                        void *stream);
+int nfm_sym_pencil_funm_backward(int dtype, int M, int fn, double p, int has_min, double vmin, int64_t n_outer,
+                                 int64_t n_inner, const nfm_operand *base, const nfm_operand *mat,
+                                 const nfm_operand *gout, const nfm_operand *gmat, void *stream);
+int nfm_sym_pencil_eig(int dtype, int M, int mode, int64_t n_outer, int64_t n_inner, const nfm_operand *base,
+                       const nfm_operand *mat, const nfm_operand *out, void *stream);
+int nfm_sym_pencil_dist_backward(int dtype, int M, int mode, int64_t n_outer, int64_t n_inner,
+                                 const nfm_operand *base, const nfm_operand *mat, const nfm_operand *gout,
+                                 const nfm_operand *grads, void *stream);
+/* largest M with a kernel for op = NFM_PENCIL_OP_*; 0 for an unknown dtype or op */
+int nfm_sym_pencil_max_order(int dtype, int op);
+
 /* -------------------------------------------------------------- batched ---- */
 
 #define NFM_FLAG_TS_PERTURB 1 /* add (max|A| - min|A|) * 1e-12 to det for N in {2,3}:

@@ -432,6 +432,70 @@ class SymFunmFn(torch.autograd.Function):
         return S._funm_backward(mat, g, code, p, vmin, dtype).to(mat.dtype), None, None, None, None
 
 
+def _to_input(g, like):
+    """a gradient of the broadcast batch shape -> the shape and dtype of the input it belongs to"""
+    return g.sum_to_size(like.shape).to(like.dtype)
+
+
+class SymPencilFunmFn(torch.autograd.Function):
+    """A^1/2 f(A^-1/2 B A^-1/2) A^1/2 of compact matrices (sym.sym_pencil_funm).  Only the two inputs are saved: the
+    backward kernel recomputes both decompositions.  With respect to `mat`: the backward kernel.  With respect to
+    `base`: for the powers (pow t, sqrt = pow 1/2, rsqrt = pow -1/2) the same kernel on swapped operands with exponent
+    1 - t (A #_t B = B #_{1-t} A); for log and exp autograd through the composition of sym_funm calls."""
+
+    @staticmethod
+    def forward(ctx, base, mat, code, p, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            y = S._pencil_forward(base, mat, code, p, dtype, None)
+        ctx.save_for_backward(base, mat)
+        ctx.cfg = (code, p, y.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import sym as S
+        from . import _lib
+        base, mat = ctx.saved_tensors
+        code, p, dtype = ctx.cfg
+        gbase = gmat = None
+        if ctx.needs_input_grad[1]:
+            gmat = _to_input(S._pencil_backward(base, mat, g, code, p, dtype), mat)
+        if ctx.needs_input_grad[0]:
+            t = {_lib.FUN['pow']: p, _lib.FUN['sqrt']: 0.5, _lib.FUN['rsqrt']: -0.5}.get(code)
+            if t is not None:
+                gbase = S._pencil_backward(mat, base, g, _lib.FUN['pow'], 1.0 - t, dtype)
+            else:
+                gbase = S._pencil_grad_composed(base.to(dtype), mat.to(dtype), g.to(dtype), code, p, 0)
+            gbase = _to_input(gbase, base)
+        return gbase, gmat, None, None, None
+
+
+class SymDistFn(torch.autograd.Function):
+    """the affine-invariant distance of compact SPD matrices or its square (sym.sym_dist): both gradients from one
+    kernel, closed forms without a divided difference (zero at a == b)."""
+
+    @staticmethod
+    def forward(ctx, a, b, mode, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            d = S._pencil_eig(a, b, mode, dtype)
+        ctx.save_for_backward(a, b)
+        ctx.cfg = (mode, d.dtype)
+        return d
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import sym as S
+        a, b = ctx.saved_tensors
+        mode, dtype = ctx.cfg
+        ga, gb = S._pencil_dist_backward(a, b, g, mode, dtype)
+        return (_to_input(ga, a) if ctx.needs_input_grad[0] else None,
+                _to_input(gb, b) if ctx.needs_input_grad[1] else None, None, None)
+
+
 # ---------------------------------------------------------------- max / min, var / std
 class PickFn(torch.autograd.Function):
     """max / min / nanmax / nanmin over dims: the cotangent goes to the selected element."""

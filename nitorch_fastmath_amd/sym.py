@@ -26,6 +26,9 @@ __all__ = [
     'sym_matmul_solve',      # extension: fused Gauss-Newton step (not in the reference)
     # extensions: spectral functions of compact symmetric matrices (not in the reference)
     'sym_funm', 'sym_expm', 'sym_logm', 'sym_sqrtm', 'sym_rsqrtm', 'sym_powm', 'sym_clampm',
+    # extensions: spectral functions of two compact symmetric matrices (not in the reference)
+    'sym_pencil_funm', 'sym_geodesic', 'sym_geomean', 'sym_logmap', 'sym_expmap', 'sym_geneigvals', 'sym_dist',
+    'sym_karcher_mean',
 ]
 import ctypes
 from math import sqrt
@@ -572,3 +575,246 @@ def sym_powm(mat, p, min=None, dtype=None, out=None):
 def sym_clampm(mat, min, dtype=None, out=None):
     """EXTENSION: projection onto `{A >= min I}`: the eigenvalues clamped from below (`sym_funm(mat, 'clamp')`)."""
     return sym_funm(mat, 'clamp', min=min, dtype=dtype, out=out)
+
+
+# ---------------------------------------------------------------- two-matrix spectral functions (extension)
+_PENCIL_CAPS = {}
+_PENCIL_FUNS = ('exp', 'log', 'sqrt', 'rsqrt', 'pow')
+
+
+def _pencil_cap(dtype, op):
+    """largest order with a kernel: the compiled table of the library (`nfm_sym_pencil_max_order`)"""
+    key = (dtype, op)
+    if key not in _PENCIL_CAPS:
+        from ._dispatch import dtype_code
+        _PENCIL_CAPS[key] = int(_lib.lib().nfm_sym_pencil_max_order(dtype_code(dtype), op))
+    return _PENCIL_CAPS[key]
+
+
+def _pencil_order(base, mat):
+    base, mat = torch.as_tensor(base), torch.as_tensor(mat)
+    if base.shape[-1] != mat.shape[-1]:
+        raise ValueError(f'the two matrices have {base.shape[-1]} and {mat.shape[-1]} components: not the same order')
+    return _nb_prm(mat.shape[-1])
+
+
+def _pencil_args(fn, p, min=None, clamp=None):
+    if min is not None or clamp is not None:
+        raise ValueError('a pencil function takes no min / clamp: clamp the operands with sym_clampm first')
+    if fn not in _PENCIL_FUNS:
+        raise ValueError(f"fn must be one of {sorted(_PENCIL_FUNS)}, got {fn!r}")
+    code, p, _ = _funm_args(fn, p, None)
+    return code, p
+
+
+def _pencil_batch(base, mat, *more):
+    batch = broadcast_shapes(base.shape[:-1], mat.shape[:-1], *[m.shape[:-1] for m in more])
+    like = mat if tuple(mat.shape[:-1]) == tuple(batch) else base
+    return batch, like
+
+
+def _pencil_forward(base, mat, code, p, dtype, out):
+    dev, dtype, (base, mat) = prepare(dtype, base, mat)
+    M = _pencil_order(base, mat)
+    if M > _pencil_cap(dtype, _lib.PENCIL_OP_FUNM):      # no kernel at this order: the composition (_sympencil.py)
+        from . import _sympencil
+        return _deliver(_sympencil.pencil_funm(base, mat, code, p), out)
+    batch, like = _pencil_batch(base, mat)
+    out, _ = _alloc_out(out, tuple(batch) + (mat.shape[-1],), dtype, dev, like=like)
+    b = Batch(batch, [expand_batch(batch, base, 1), expand_batch(batch, mat, 1), out], [1, 1, 1])
+    launch(_lib.lib().nfm_sym_pencil_funm, dev, dtype, (M, code, p, 0, 0.0), b)
+    return out
+
+
+def _pencil_backward(base, mat, gout, code, p, dtype):
+    """gradient with respect to `mat`, of the broadcast batch shape (the composition above the cap: of `mat`'s own
+    shape; the caller sums to the input's shape either way)"""
+    dev, dtype, (base, mat, gout) = prepare(dtype, base, mat, gout)
+    M = _pencil_order(base, mat)
+    if M > _pencil_cap(dtype, _lib.PENCIL_OP_FUNM_BACKWARD):
+        return _pencil_grad_composed(base, mat, gout, code, p, 1)
+    batch, like = _pencil_batch(base, mat, gout)
+    gmat, _ = _alloc_out(None, tuple(batch) + (mat.shape[-1],), dtype, dev, like=like)
+    b = Batch(batch, [expand_batch(batch, base, 1), expand_batch(batch, mat, 1), expand_batch(batch, gout, 1), gmat],
+              [1, 1, 1, 1])
+    launch(_lib.lib().nfm_sym_pencil_funm_backward, dev, dtype, (M, code, p, 0, 0.0), b)
+    return gmat
+
+
+def _pencil_grad_composed(base, mat, gout, code, p, which):
+    """gradient of the composition (_sympencil.py) with respect to base (which = 0) or mat (1), input-shaped"""
+    from . import _sympencil
+    with torch.enable_grad():
+        ops = [base.detach(), mat.detach()]
+        ops[which] = ops[which].requires_grad_(True)
+        y = _sympencil.pencil_funm(ops[0], ops[1], code, p)
+        (g,) = torch.autograd.grad(y, ops[which], gout.expand(y.shape))
+    return g
+
+
+def _pencil_eig(base, mat, mode, dtype, out=None):
+    dev, dtype, (base, mat) = prepare(dtype, base, mat)
+    M = _pencil_order(base, mat)
+    if M > _pencil_cap(dtype, _lib.PENCIL_OP_EIG):
+        from . import _sympencil
+        res = (_sympencil.geneigvals(base, mat) if mode == _lib.PENCIL_EIG
+               else _sympencil.dist(base, mat, squared=mode == _lib.PENCIL_DIST2))
+        return _deliver(res, out)
+    batch, _ = _pencil_batch(base, mat)
+    if mode == _lib.PENCIL_EIG:
+        out, _ = _alloc_out(out, tuple(batch) + (M,), dtype, dev)
+        rec = out
+    else:
+        out, _ = _alloc_out(out, tuple(batch), dtype, dev)
+        rec = out.unsqueeze(-1)
+    b = Batch(batch, [expand_batch(batch, base, 1), expand_batch(batch, mat, 1), rec], [1, 1, 1])
+    launch(_lib.lib().nfm_sym_pencil_eig, dev, dtype, (M, mode), b)
+    return out
+
+
+def _pencil_dist_backward(base, mat, gout, mode, dtype):
+    """(gradient with respect to base, with respect to mat) of the distance, both of the broadcast batch shape: two
+    views of one (..., 2, K) tensor (the composition above the cap: each of its input's own shape, already summed over
+    the broadcast dims; the caller sums to the input's shape either way, a no-op there)"""
+    dev, dtype, (base, mat, gout) = prepare(dtype, base, mat, gout)
+    M = _pencil_order(base, mat)
+    batch, _ = _pencil_batch(base, mat)
+    if M > _pencil_cap(dtype, _lib.PENCIL_OP_DIST_BACKWARD):
+        from . import _sympencil
+        with torch.enable_grad():
+            a, b = base.detach().requires_grad_(True), mat.detach().requires_grad_(True)
+            d = _sympencil.dist(a, b, squared=mode == _lib.PENCIL_DIST2)
+            ga, gb = torch.autograd.grad(d, (a, b), gout.expand(d.shape))
+        return ga, gb
+    K = mat.shape[-1]
+    grads = torch.empty(tuple(batch) + (2, K), dtype=dtype, device=dev)
+    b = Batch(batch, [expand_batch(batch, base, 1), expand_batch(batch, mat, 1),
+                      expand_batch(batch, gout.unsqueeze(-1), 1), grads.view(tuple(batch) + (2 * K,))], [1, 1, 1, 1])
+    launch(_lib.lib().nfm_sym_pencil_dist_backward, dev, dtype, (M, mode), b)
+    return grads[..., 0, :], grads[..., 1, :]
+
+
+def sym_pencil_funm(base, mat, fn, p=None, dtype=None, out=None, min=None, clamp=None):
+    r"""EXTENSION (not in the reference): `A^{1/2} f(A^{-1/2} B A^{-1/2}) A^{1/2}` for compact `A = base` (symmetric
+    positive definite) and compact symmetric `B = mat`, compact out, in ONE kernel.
+
+    `A = V L V^T`, `W = V L^{-1/2}`, `W^T B W = Q M Q^T`: the `mu_i` are the generalised eigenvalues of
+    `B x = mu A x`, and the result is `Z f(M) Z^T` with `Z = V L^{1/2} Q`.  Both decompositions stay in the registers
+    of one lane: each record is read once and the result written once, instead of the chain
+    `sym_rsqrtm -> sym_to_full -> sym_matmul -> sym_funm -> sym_matmul` and its three decompositions.
+
+    Parameters
+    ----------
+    base, mat : `(..., M*(M+1)//2) tensor`; the batch dims broadcast without a copy
+    fn : {'exp', 'log', 'sqrt', 'rsqrt', 'pow'}; `p` : the exponent of 'pow'
+        'pow' with exponent t is the point `A #_t B` of the geodesic, 'log' / 'exp' the Riemannian log / exp map at A.
+        There is no `min` / `clamp` here (a `ValueError`).
+    dtype, out : as `sym_funm`; `out=mat` is allowed.
+
+    A record with an entry that is not finite, a base that is not positive definite, or a `mu` outside the domain
+    of `f` gives NaN in every component of its result and gradients; its neighbours are untouched.  No exception, no
+    host synchronisation: a call (forward and backward) can be captured in a graph.
+
+    Differentiable once.  With respect to `mat`: `X [(Z^T G Z) o F] X^T`, `X = Z^{-T}`, with the closed-form divided
+    differences of `sym_funm`, regular at repeated `mu`.  With respect to `base` for 'pow' / 'sqrt' / 'rsqrt': the
+    same kernel through `A #_t B = B #_{1-t} A` (which needs `mat` positive definite as well); for 'log' / 'exp':
+    autograd through the composition of `sym_funm` calls.  Orders above the compiled caps
+    (`nfm_sym_pencil_max_order`) run that composition throughout.
+    """
+    code, p = _pencil_args(fn, p, min, clamp)
+    _pencil_order(base, mat)
+    if needs_grad(base, mat):
+        _grad_guard(out)
+        from ._autograd import SymPencilFunmFn
+        return SymPencilFunmFn.apply(torch.as_tensor(base), torch.as_tensor(mat), code, p, dtype)
+    return _pencil_forward(base, mat, code, p, dtype, out)
+
+
+def sym_geodesic(a, b, t, dtype=None, out=None):
+    """EXTENSION: the point `a #_t b = a^{1/2} (a^{-1/2} b a^{-1/2})^t a^{1/2}` of the affine-invariant geodesic from
+    `a` (t = 0) to `b` (t = 1), compact SPD in and out (`sym_pencil_funm(a, b, 'pow', t)`)."""
+    return sym_pencil_funm(a, b, 'pow', p=t, dtype=dtype, out=out)
+
+
+def sym_geomean(a, b, dtype=None, out=None):
+    """EXTENSION: the geometric mean `a # b` of two compact SPD matrices (`sym_geodesic(a, b, 1/2)`)."""
+    return sym_pencil_funm(a, b, 'sqrt', dtype=dtype, out=out)
+
+
+def sym_logmap(base, mat, dtype=None, out=None):
+    """EXTENSION: the Riemannian log map `Log_base(mat)` of the affine-invariant metric: the compact symmetric
+    tangent vector at `base` that points to `mat` (`sym_pencil_funm(base, mat, 'log')`)."""
+    return sym_pencil_funm(base, mat, 'log', dtype=dtype, out=out)
+
+
+def sym_expmap(base, tangent, dtype=None, out=None):
+    """EXTENSION: the Riemannian exp map `Exp_base(tangent)`, the inverse of `sym_logmap`; `tangent` is any compact
+    symmetric matrix (`sym_pencil_funm(base, tangent, 'exp')`)."""
+    return sym_pencil_funm(base, tangent, 'exp', dtype=dtype, out=out)
+
+
+def sym_geneigvals(mat, base, dtype=None, out=None):
+    """EXTENSION: the generalised eigenvalues of `mat x = mu base x`, ascending, `(..., M)`: compact symmetric `mat`,
+    compact SPD `base` (the argument order of `scipy.linalg.eigh(a, b)`).  NaN records as `sym_pencil_funm`.
+    With an operand that requires grad the composition of `sym_funm` calls and `torch.linalg.eigvalsh` runs."""
+    _pencil_order(base, mat)
+    if needs_grad(mat, base):
+        _grad_guard(out)
+        from . import _sympencil
+        dev, dtype, (base, mat) = prepare(dtype, base, mat, grad_ok=True)
+        return _sympencil.geneigvals(base, mat)
+    return _pencil_eig(base, mat, _lib.PENCIL_EIG, dtype, out)
+
+
+def sym_dist(a, b, squared=False, dtype=None, out=None):
+    r"""EXTENSION: the affine-invariant distance `d(a, b) = ||log(a^{-1/2} b a^{-1/2})||_F` of compact SPD matrices
+    (`squared=True`: `d^2 = sum_i log^2 mu_i`), `(...)`.
+
+    Differentiable once with respect to both, by closed forms with no divided difference:
+    `d d^2 / d b = X diag(2 log mu / mu) X^T`, `d d^2 / d a = -X diag(2 log mu) X^T`: finite, and exactly zero, at
+    `a = b`.  The gradient of `d` itself carries the factor `1 / (2 d)` and is DEFINED as 0 at `d = 0` (a
+    subgradient: `d` has a kink there); minimise `squared=True`.  NaN records as `sym_pencil_funm`.
+    """
+    _pencil_order(a, b)
+    mode = _lib.PENCIL_DIST2 if squared else _lib.PENCIL_DIST
+    if needs_grad(a, b):
+        _grad_guard(out)
+        from ._autograd import SymDistFn
+        return SymDistFn.apply(torch.as_tensor(a), torch.as_tensor(b), mode, dtype)
+    return _pencil_eig(a, b, mode, dtype, out)
+
+
+def sym_karcher_mean(mats, dim=0, weights=None, max_iter=8):
+    r"""EXTENSION: the Karcher (Frechet) mean of compact SPD matrices along `dim` under the affine-invariant metric.
+
+    Starts at the log-Euclidean mean `M = sym_expm(sum_i w_i sym_logm(A_i))` and repeats
+    `M <- sym_expmap(M, sum_i w_i sym_logmap(M, A_i))` `max_iter` times; `M` is broadcast along `dim` with stride 0,
+    so it is read in place.  A fixed number of iterations and no host synchronisation: capturable in a graph.
+    Not differentiable.  The step-one iteration converges linearly, by a factor that grows with the squared geodesic
+    diameter of the set: 8 steps reach the rounding level for matrices within about 0.5 of each other (`sym_dist`);
+    widely dispersed sets want a larger `max_iter` (32 for distances around 2).
+
+    mats : `(..., n, ..., K)` with the n matrices of a set along `dim` (not the last); weights : `(n,)`, optional
+    (normalised to sum 1; default uniform) -> the input shape without `dim`.
+    """
+    mats = torch.as_tensor(mats)
+    nd = mats.dim()
+    dim = dim + nd if dim < 0 else dim
+    if not 0 <= dim < nd - 1:
+        raise ValueError(f'dim {dim} is not a batch dimension of a tensor with {nd} dimensions')
+    n = mats.shape[dim]
+    with torch.no_grad():
+        mats = mats.detach()
+        if weights is None:
+            w = torch.full((n,), 1.0 / n, dtype=mats.dtype, device=mats.device)
+        else:
+            w = torch.as_tensor(weights, dtype=mats.dtype, device=mats.device)
+            if w.shape != (n,):
+                raise ValueError(f'weights must have shape ({n},), got {tuple(w.shape)}')
+            w = w / w.sum()
+        w = w.reshape((n,) + (1,) * (nd - 1 - dim))
+        mean = sym_expm((w * sym_logm(mats)).sum(dim))
+        for _ in range(int(max_iter)):
+            step = (w * sym_logmap(mean.unsqueeze(dim).expand(mats.shape), mats)).sum(dim)
+            mean = sym_expmap(mean, step)
+    return mean
