@@ -3,6 +3,7 @@ broadcast normalisation and the two-level batch collapse (no data movement unles
 the broadcast batch genuinely needs more than two stride levels), and the one way into
 the library: `prepare` checks the operands, `launch` / `call` run an entry point."""
 from ctypes import byref
+import functools
 import torch
 from . import _lib
 
@@ -14,6 +15,13 @@ def dtype_code(dtype):
         return _DTYPES[dtype]
     except KeyError:
         raise TypeError(f'nitorch_fastmath_amd supports float32 and float64 tensors, got {dtype}') from None
+
+
+@functools.lru_cache(maxsize=None)
+def max_order(entry, dtype, code):
+    """largest order with a kernel: the library's compiled table `entry` (an `nfm_*_max_order`) for a dtype and the
+    entry's own second argument (a direction or an op code), asked once per key"""
+    return int(getattr(_lib.lib(), entry)(dtype_code(dtype), int(code)))
 
 
 def require_gpu(*tensors):

@@ -14,7 +14,7 @@ decompositions of general square matrices up to 8x8 by a one-sided Jacobi SVD in
 __all__ = ['batchmatvec', 'batchdet', 'batchinv', 'batchsvdvals', 'batchsvd', 'batchpolar']
 import torch
 from . import _lib
-from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, max_order, needs_grad, prepare
 
 
 def _like_or_contiguous(like, shape, dtype, dev):
@@ -93,7 +93,6 @@ def batchmatvec(mat, vec):
 
 
 # ---------------------------------------------------------------- singular values, SVD, polar (extension)
-_POLAR_CAPS = {}
 # (dtype, op, n, channel_first) measured slower than the torch composition the call would otherwise take
 # (profiles/polar_table.md): routed back to it.  None so far.
 _POLAR_TORCH_ROUTE = frozenset()
@@ -102,13 +101,9 @@ _POLAR_TORCH_ROUTE = frozenset()
 def polar_max_order(dtype, op):
     """largest order with a kernel: the compiled table of the library (`nfm_polar_max_order`); `op` is one of
     'svdvals', 'svd', 'polar', 'polar_backward'"""
-    from ._dispatch import dtype_code
     code = {'svdvals': _lib.POLAR_SVDVALS, 'svd': _lib.POLAR_SVD, 'polar': _lib.POLAR_POLAR,
             'polar_backward': _lib.POLAR_POLAR_BACKWARD}[op]
-    key = (dtype, code)
-    if key not in _POLAR_CAPS:
-        _POLAR_CAPS[key] = int(_lib.lib().nfm_polar_max_order(dtype_code(dtype), code))
-    return _POLAR_CAPS[key]
+    return max_order('nfm_polar_max_order', dtype, code)
 
 
 def _channel_first(a):

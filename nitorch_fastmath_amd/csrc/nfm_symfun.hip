@@ -4,16 +4,17 @@
 // neither on the deflation order nor on the eigenvector signs, and the fast mode is the one held to 16 n eps on
 // repeated and clustered spectra), apply f to the eigenvalues, recompose the upper triangle, write K values.  The
 // backward recomputes the decomposition from the saved input (saving V would cost N^2 values per record in HBM)
-// and evaluates V [(V^T G V) o F] V^T with the closed-form divided differences of nfm_symfun_ops.hpp.
+// and evaluates V [(V^T G V) o F] V^T with the closed-form divided differences of nfm_symfun_ops.hpp.  The
+// expansion of a record and the sweeps' arguments are those of nfm_spectral.hpp, shared with the pencil kernels.
 // fn, p and the clamp are run-time members of Params (a wave-uniform switch): the instantiations are
 // (dtype, N, direction) x the layout kinds of rec_launch.
 #include "nfm_record_kernel.hpp"
-#include "nfm_qr_core.hpp"
-#include "nfm_symfun_ops.hpp"
+#include "nfm_spectral.hpp"
 
 // This file is compiled seventeen times (-DNFM_SYMFUN_PART=0..16).  Part 0: the entry points, the caps and the CPU
 // evaluation of the scalar pieces.  Parts 1..16: the kernels of one (dtype, direction, pair of orders):
-// part = 1 + dtype * 8 + backward * 4 + pair, pair p = orders 2p + 1 and 2p + 2.
+// part = 1 + dtype * 8 + backward * 4 + pair, pair p = orders 2p + 1 and 2p + 2.  Each of them defines its own
+// specialisation of symfun_part<PART>; part 0 reaches them through switch_order<16>.
 #ifndef NFM_SYMFUN_PART
 #error "compile with -DNFM_SYMFUN_PART=0..16"
 #endif
@@ -28,25 +29,6 @@ using symfun::FunParams;
 // bytes of scratch per lane, so the order is left to the caller's route)
 constexpr int kSymFunCap[2][2] = {{8, 8}, {8, 7}}; // [dtype][backward]
 constexpr bool symfun_fits(bool f64, bool bwd, int N) { return N >= 1 && N <= kSymFunCap[f64 ? 1 : 0][bwd ? 1 : 0]; }
-
-// the sweeps' arguments: those of eig_sym's defaults (the fast sweeps floor tol at the working precision)
-constexpr int kSymFunMaxIter = 1024;
-constexpr double kSymFunTol = 1e-32;
-
-// compact record -> the (mirrored) matrix eig_sym1 reads; a record with an entry that is not finite is replaced by
-// the identity (its result is NaN anyway, and the sweeps of a NaN matrix would run to max_iter)
-template <typename T, int N>
-__device__ __forceinline__ bool symfun_expand(const T (&r)[sym_k(N)], T (&a)[N][N])
-{
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < sym_k(N); ++k) bad |= !symfun::finite_t(r[k]);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) a[i][j] = bad ? T(i == j) : r[sym_idx(N, i, j)];
-    return bad;
-}
 
 template <typename T, int N>
 struct SymFunOp {
@@ -71,8 +53,8 @@ struct SymFunOp {
             bool bad;
             {
                 T a[N][N], up[N][N];
-                bad = symfun_expand<T, N>(r, a);
-                qr::eig_sym1<T, N, true, true>(a, u, up, f, N, kSymFunMaxIter, kSymFunTol);
+                bad = spectral::expand<T, N>(r, a);
+                qr::eig_sym1<T, N, true, true>(a, u, up, f, N, spectral::kMaxIter, spectral::kTol);
             } // a and up die here
 #pragma unroll
             for (int k = 0; k < N; ++k) {
@@ -80,7 +62,9 @@ struct SymFunOp {
                 bad |= !symfun::in_domain(q, x);
                 f[k] = symfun::fval(q, x);
             }
-            // Y_ij = sum_k V_ik f_k V_jk, i <= j
+            // Y_ij = sum_k V_ik f_k V_jk, i <= j: spectral::recompose<T, N, 1>, written out.  Built from the shared block
+            // the float64 kernels of N = 3 and N = 8 need more registers and lose a wave per SIMD (a block's loops are
+            // unrolled before it is inlined; u, indexed by literals only from then on, is promoted to one vector).
 #pragma unroll
             for (int i = 0; i < N; ++i) {
                 T t[N];
@@ -119,11 +103,13 @@ struct SymFunBwdOp {
             bool bad;
             {
                 T a[N][N], up[N][N];
-                bad = symfun_expand<T, N>(r, a);
-                qr::eig_sym1<T, N, true, true>(a, u, up, lam, N, kSymFunMaxIter, kSymFunTol);
-            }
+                bad = spectral::expand<T, N>(r, a);
+                qr::eig_sym1<T, N, true, true>(a, u, up, lam, N, spectral::kMaxIter, spectral::kTol);
+            } // a and up die here
 #pragma unroll
             for (int k = 0; k < N; ++k) bad |= !symfun::in_domain(q, symfun::clamp_min(q, lam[k]));
+            // (these three steps are written out a second time, with Z and X for V, in PencilFunBwdOp of nfm_sympencil.hip:
+            // built from shared blocks, the float32 kernel of N = 8 here needs a private segment)
             // W = V^T G V (symmetric, compact), G_ii = g_ii, G_ij = g_ij / 2: column l of G V, then row k <= l
             T w[K];
 #pragma unroll
@@ -175,19 +161,15 @@ struct SymFunBwdOp {
 };
 
 // one launcher per part: (M, mat, gout or NULL, out)
-#define NFM_SYMFUN_DECL(p)                                                                                        \
-    int symfun_part_##p(int M, const nfm_operand *a, const nfm_operand *g, const nfm_operand *o, int64_t no, int64_t ni, \
-                        const FunParams &q, void *stream);
-NFM_SYMFUN_DECL(1) NFM_SYMFUN_DECL(2) NFM_SYMFUN_DECL(3) NFM_SYMFUN_DECL(4) NFM_SYMFUN_DECL(5) NFM_SYMFUN_DECL(6)
-NFM_SYMFUN_DECL(7) NFM_SYMFUN_DECL(8) NFM_SYMFUN_DECL(9) NFM_SYMFUN_DECL(10) NFM_SYMFUN_DECL(11) NFM_SYMFUN_DECL(12)
-NFM_SYMFUN_DECL(13) NFM_SYMFUN_DECL(14) NFM_SYMFUN_DECL(15) NFM_SYMFUN_DECL(16)
-#undef NFM_SYMFUN_DECL
+#define NFM_SYMFUN_ARGS                                                                                                \
+    int M, const nfm_operand *a, const nfm_operand *g, const nfm_operand *o, int64_t no, int64_t ni, const FunParams &q, \
+        void *stream
+template <int PART>
+int symfun_part(NFM_SYMFUN_ARGS);
 
 #if NFM_SYMFUN_PART >= 1
-#define NFM_SYMFUN_NAME2(p) symfun_part_##p
-#define NFM_SYMFUN_NAME1(p) NFM_SYMFUN_NAME2(p)
-int NFM_SYMFUN_NAME1(NFM_SYMFUN_PART)(int M, const nfm_operand *a, const nfm_operand *g, const nfm_operand *o, int64_t no,
-                                      int64_t ni, const FunParams &q, void *stream)
+template <>
+int symfun_part<NFM_SYMFUN_PART>(NFM_SYMFUN_ARGS)
 {
     constexpr int part = NFM_SYMFUN_PART - 1;
     constexpr bool F64 = part / 8 != 0, BWD = (part / 4) % 2 != 0;
@@ -218,23 +200,17 @@ static int symfun_check(int dtype, int M, int fn, double p, int has_min, double 
 {
     const int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (fn < NFM_FUN_EXP || fn > NFM_FUN_CLAMP) return NFM_EINVAL;
-    if (!symfun_fits(dtype == NFM_F64, backward != 0, M)) return NFM_ESIZE;
-    if (!std::isfinite(p) || !std::isfinite(vmin)) return NFM_EINVAL;
-    if (fn == NFM_FUN_CLAMP && !has_min) return NFM_EINVAL;
-    return NFM_OK;
+    return symfun::check_fun(true, fn, p, has_min, vmin, symfun_fits(dtype == NFM_F64, backward != 0, M));
 }
 
 static int symfun_dispatch(int dtype, int M, int backward, const nfm_operand *a, const nfm_operand *g,
                            const nfm_operand *o, int64_t no, int64_t ni, const FunParams &q, void *stream)
 {
-    using Fn = int (*)(int, const nfm_operand *, const nfm_operand *, const nfm_operand *, int64_t, int64_t,
-                       const FunParams &, void *);
-    static const Fn table[16] = {symfun_part_1,  symfun_part_2,  symfun_part_3,  symfun_part_4,
-                                 symfun_part_5,  symfun_part_6,  symfun_part_7,  symfun_part_8,
-                                 symfun_part_9,  symfun_part_10, symfun_part_11, symfun_part_12,
-                                 symfun_part_13, symfun_part_14, symfun_part_15, symfun_part_16};
-    return table[(dtype == NFM_F64 ? 8 : 0) + (backward ? 4 : 0) + (M - 1) / 2](M, a, g, o, no, ni, q, stream);
+    const int part = (dtype == NFM_F64 ? 8 : 0) + (backward ? 4 : 0) + (M - 1) / 2;
+    return switch_order<16>(part + 1, NFM_ESIZE, [&](auto p) {
+        constexpr int P = p;
+        return symfun_part<P>(M, a, g, o, no, ni, q, stream);
+    });
 }
 
 template <typename T>
@@ -285,9 +261,7 @@ int nfm_sym_funm_host_eval(int dtype, int fn, double p, int has_min, double vmin
                            void *dd)
 {
     if (dtype != NFM_F32 && dtype != NFM_F64) return NFM_EDTYPE;
-    if (n < 0 || fn < NFM_FUN_EXP || fn > NFM_FUN_CLAMP) return NFM_EINVAL;
-    if (!std::isfinite(p) || !std::isfinite(vmin)) return NFM_EINVAL;
-    if (fn == NFM_FUN_CLAMP && !has_min) return NFM_EINVAL;
+    if (n < 0 || symfun::check_fun(true, fn, p, has_min, vmin, true)) return NFM_EINVAL;
     if (n > 0 && (lam == nullptr || f == nullptr || dd == nullptr)) return NFM_EINVAL;
     const FunParams q{fn, has_min != 0, p, vmin};
     if (dtype == NFM_F32)

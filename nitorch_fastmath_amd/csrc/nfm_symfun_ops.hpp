@@ -33,6 +33,18 @@ struct FunParams {
     double vmin; // the clamp
 };
 
+// The argument check of a function code at an entry point, in the documented order: the code, then the cap (`fits`),
+// then the values.  `clamp`: the entry takes a lower clamp (has_min, vmin) and NFM_FUN_CLAMP; a pencil takes neither
+// and passes vmin = 0.
+inline int check_fun(bool clamp, int fn, double p, int has_min, double vmin, bool fits)
+{
+    if (fn < NFM_FUN_EXP || fn > (clamp ? NFM_FUN_CLAMP : NFM_FUN_POW) || (has_min && !clamp)) return NFM_EINVAL;
+    if (!fits) return NFM_ESIZE;
+    if (!std::isfinite(p) || !std::isfinite(vmin)) return NFM_EINVAL;
+    if (fn == NFM_FUN_CLAMP && !has_min) return NFM_EINVAL;
+    return NFM_OK;
+}
+
 NFM_HD float exp_t(float x) { return expf(x); }
 NFM_HD double exp_t(double x) { return exp(x); }
 NFM_HD float log_t(float x) { return logf(x); }

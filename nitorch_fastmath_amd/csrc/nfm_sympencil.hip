@@ -4,15 +4,14 @@
 // their gradient with respect to B, the generalised eigenvalues of B x = mu A x, the affine-invariant distance
 // d = ||log(A^-1/2 B A^-1/2)||_F and its gradients.  One record per lane through rec_kernel: both compact records are
 // read once, the two decompositions and the products between them stay in the lane's registers
-// (nfm_sympencil_ops.hpp), the result is written once.
+// (nfm_sympencil_ops.hpp; the blocks shared with sym_funm are in nfm_spectral.hpp), the result is written once.
 #include "nfm_record_kernel.hpp"
-#include "nfm_qr_core.hpp"
-#include "nfm_symfun_ops.hpp"
 #include "nfm_sympencil_ops.hpp"
 
 // This file is compiled 33 times (-DNFM_SYMPENCIL_PART=0..32).  Part 0: the entry points and the caps.
 // Parts 1..32: the kernels of one (dtype, op, pair of orders): part = 1 + dtype * 16 + op * 4 + pair, pair p = orders
-// 2p + 1 and 2p + 2; op: 0 function, 1 its gradient, 2 eigenvalues / distance, 3 gradients of the distance.
+// 2p + 1 and 2p + 2; op: 0 function, 1 its gradient, 2 eigenvalues / distance, 3 gradients of the distance.  Each of
+// them defines its own specialisation of sympencil_part<PART>; part 0 reaches them through switch_order<32>.
 #ifndef NFM_SYMPENCIL_PART
 #error "compile with -DNFM_SYMPENCIL_PART=0..32"
 #endif
@@ -55,7 +54,7 @@ struct PencilFunOp {
                 {
                     T c[N][N], up[N][N];
                     bad = sympencil::whiten<T, N>(ra, rb, z, lam, c);
-                    qr::eig_sym1<T, N, true, true>(c, qq, up, f, N, sympencil::kMaxIter, sympencil::kTol);
+                    qr::eig_sym1<T, N, true, true>(c, qq, up, f, N, spectral::kMaxIter, spectral::kTol);
                 }
                 sympencil::times_q<T, N, true>(z, lam, qq); // Z = W L Q
             }
@@ -64,7 +63,7 @@ struct PencilFunOp {
                 bad |= !symfun::in_domain(q, f[k]);
                 f[k] = symfun::fval(q, f[k]);
             }
-            sympencil::recompose<T, N>(z, f, bad, T(1), o);
+            spectral::recompose<T, N, 1>(z, f, bad, o);
         }
     }
 };
@@ -95,7 +94,7 @@ struct PencilFunBwdOp {
                 {
                     T c[N][N], up[N][N];
                     bad = sympencil::whiten<T, N>(ra, rb, x, lam, c);
-                    qr::eig_sym1<T, N, true, true>(c, qq, up, mu, N, sympencil::kMaxIter, sympencil::kTol);
+                    qr::eig_sym1<T, N, true, true>(c, qq, up, mu, N, spectral::kMaxIter, spectral::kTol);
                 }
 #pragma unroll
                 for (int i = 0; i < N; ++i)
@@ -106,6 +105,7 @@ struct PencilFunBwdOp {
             }
 #pragma unroll
             for (int k = 0; k < N; ++k) bad |= !symfun::in_domain(q, mu[k]);
+            // (the three steps of SymFunBwdOp, nfm_symfun.hip, with Z and X for V: see there why they are written twice)
             // H = Z^T Gbar Z (symmetric, compact), Gbar_ii = g_ii, Gbar_ij = g_ij / 2: column l of Gbar Z, then rows k <= l
             T h[K];
 #pragma unroll
@@ -177,7 +177,7 @@ struct PencilEigOp {
         } else {
             T w[N][N], lam[N], c[N][N], up[N][N];
             bad = sympencil::whiten<T, N>(ra, rb, w, lam, c);
-            qr::eig_sym1<T, N, false, true>(c, w, up, mu, N, sympencil::kMaxIter, sympencil::kTol);
+            qr::eig_sym1<T, N, false, true>(c, w, up, mu, N, spectral::kMaxIter, spectral::kTol);
         }
         if constexpr (DIST) {
             T d2 = T(0);
@@ -225,7 +225,7 @@ struct PencilDistBwdOp {
             {
                 T c[N][N], up[N][N];
                 bad = sympencil::whiten<T, N>(ra, rb, x, lam, c);
-                qr::eig_sym1<T, N, true, true>(c, qq, up, mu, N, sympencil::kMaxIter, sympencil::kTol);
+                qr::eig_sym1<T, N, true, true>(c, qq, up, mu, N, spectral::kMaxIter, spectral::kTol);
             }
             sympencil::times_q<T, N, false>(x, lam, qq); // X = W Q
         }
@@ -250,8 +250,8 @@ struct PencilDistBwdOp {
             fb[k] *= coef;
         }
         bad |= !symfun::finite_t(g[0]);
-        sympencil::recompose<T, N>(x, fa, bad, T(2), &o[0]);
-        sympencil::recompose<T, N>(x, fb, bad, T(2), &o[K]);
+        spectral::recompose<T, N, 2>(x, fa, bad, &o[0]);
+        spectral::recompose<T, N, 2>(x, fb, bad, &o[K]);
     }
 };
 
@@ -260,23 +260,15 @@ struct PencilArgs {
     FunParams fun;
     EigParams eig;
 };
-#define NFM_SYMPENCIL_DECL(p)                                                                                          \
-    int sympencil_part_##p(int M, const nfm_operand *a, const nfm_operand *b, const nfm_operand *g, const nfm_operand *o, \
-                           int64_t no, int64_t ni, const PencilArgs &q, void *stream);
-NFM_SYMPENCIL_DECL(1) NFM_SYMPENCIL_DECL(2) NFM_SYMPENCIL_DECL(3) NFM_SYMPENCIL_DECL(4) NFM_SYMPENCIL_DECL(5)
-NFM_SYMPENCIL_DECL(6) NFM_SYMPENCIL_DECL(7) NFM_SYMPENCIL_DECL(8) NFM_SYMPENCIL_DECL(9) NFM_SYMPENCIL_DECL(10)
-NFM_SYMPENCIL_DECL(11) NFM_SYMPENCIL_DECL(12) NFM_SYMPENCIL_DECL(13) NFM_SYMPENCIL_DECL(14) NFM_SYMPENCIL_DECL(15)
-NFM_SYMPENCIL_DECL(16) NFM_SYMPENCIL_DECL(17) NFM_SYMPENCIL_DECL(18) NFM_SYMPENCIL_DECL(19) NFM_SYMPENCIL_DECL(20)
-NFM_SYMPENCIL_DECL(21) NFM_SYMPENCIL_DECL(22) NFM_SYMPENCIL_DECL(23) NFM_SYMPENCIL_DECL(24) NFM_SYMPENCIL_DECL(25)
-NFM_SYMPENCIL_DECL(26) NFM_SYMPENCIL_DECL(27) NFM_SYMPENCIL_DECL(28) NFM_SYMPENCIL_DECL(29) NFM_SYMPENCIL_DECL(30)
-NFM_SYMPENCIL_DECL(31) NFM_SYMPENCIL_DECL(32)
-#undef NFM_SYMPENCIL_DECL
+#define NFM_SYMPENCIL_ARGS                                                                                             \
+    int M, const nfm_operand *a, const nfm_operand *b, const nfm_operand *g, const nfm_operand *o, int64_t no,          \
+        int64_t ni, const PencilArgs &q, void *stream
+template <int PART>
+int sympencil_part(NFM_SYMPENCIL_ARGS);
 
 #if NFM_SYMPENCIL_PART >= 1
-#define NFM_SYMPENCIL_NAME2(p) sympencil_part_##p
-#define NFM_SYMPENCIL_NAME1(p) NFM_SYMPENCIL_NAME2(p)
-int NFM_SYMPENCIL_NAME1(NFM_SYMPENCIL_PART)(int M, const nfm_operand *a, const nfm_operand *b, const nfm_operand *g,
-                                            const nfm_operand *o, int64_t no, int64_t ni, const PencilArgs &q, void *stream)
+template <>
+int sympencil_part<NFM_SYMPENCIL_PART>(NFM_SYMPENCIL_ARGS)
 {
     constexpr int part = NFM_SYMPENCIL_PART - 1;
     constexpr bool F64 = part / 16 != 0;
@@ -311,16 +303,11 @@ using namespace nfm;
 static int sympencil_dispatch(int dtype, int M, int op, const nfm_operand *a, const nfm_operand *b, const nfm_operand *g,
                               const nfm_operand *o, int64_t no, int64_t ni, const PencilArgs &q, void *stream)
 {
-    using Fn = int (*)(int, const nfm_operand *, const nfm_operand *, const nfm_operand *, const nfm_operand *, int64_t,
-                       int64_t, const PencilArgs &, void *);
-    static const Fn table[32] = {
-        sympencil_part_1,  sympencil_part_2,  sympencil_part_3,  sympencil_part_4,  sympencil_part_5,  sympencil_part_6,
-        sympencil_part_7,  sympencil_part_8,  sympencil_part_9,  sympencil_part_10, sympencil_part_11, sympencil_part_12,
-        sympencil_part_13, sympencil_part_14, sympencil_part_15, sympencil_part_16, sympencil_part_17, sympencil_part_18,
-        sympencil_part_19, sympencil_part_20, sympencil_part_21, sympencil_part_22, sympencil_part_23, sympencil_part_24,
-        sympencil_part_25, sympencil_part_26, sympencil_part_27, sympencil_part_28, sympencil_part_29, sympencil_part_30,
-        sympencil_part_31, sympencil_part_32};
-    return table[(dtype == NFM_F64 ? 16 : 0) + op * 4 + (M - 1) / 2](M, a, b, g, o, no, ni, q, stream);
+    const int part = (dtype == NFM_F64 ? 16 : 0) + op * 4 + (M - 1) / 2;
+    return switch_order<32>(part + 1, NFM_ESIZE, [&](auto p) {
+        constexpr int P = p;
+        return sympencil_part<P>(M, a, b, g, o, no, ni, q, stream);
+    });
 }
 
 // the checks of nfm_sym_funm in its order: the batch, the function code, the cap, p finite (then the operands)
@@ -328,10 +315,7 @@ static int pencil_fun_check(int dtype, int M, int fn, double p, int has_min, int
 {
     const int rc = check_batch(dtype, n_outer, n_inner, {M});
     if (rc) return rc;
-    if (fn < NFM_FUN_EXP || fn > NFM_FUN_POW || has_min) return NFM_EINVAL; // no clamp for a pencil
-    if (!sympencil_fits(dtype == NFM_F64, op, M)) return NFM_ESIZE;
-    if (!std::isfinite(p)) return NFM_EINVAL;
-    return NFM_OK;
+    return symfun::check_fun(false, fn, p, has_min, 0.0, sympencil_fits(dtype == NFM_F64, op, M)); // no clamp
 }
 
 static int pencil_eig_check(int dtype, int M, int mode, bool dist_only, int op, int64_t n_outer, int64_t n_inner)

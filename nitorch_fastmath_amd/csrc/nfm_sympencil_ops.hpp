@@ -11,36 +11,16 @@
 // affine-invariant distance is sum_i log^2 mu_i with the gradients X diag(2 log mu / mu) X^T (B) and
 // -X diag(2 log mu) X^T (A): no divided difference, exact at A = B.
 #pragma once
-#include "nfm_qr_core.hpp"
-#include "nfm_symfun_ops.hpp"
+#include "nfm_spectral.hpp"
 
 namespace nfm {
 namespace sympencil {
-
-// the sweeps' arguments: those of sym_funm
-constexpr int kMaxIter = 1024;
-constexpr double kTol = 1e-32;
 
 // what nfm_sym_pencil_eig returns
 enum { MODE_EIG = 0, MODE_DIST2 = 1, MODE_DIST = 2 };
 struct EigParams {
     int mode;
 };
-
-// compact record -> the (mirrored) matrix eig_sym1 reads; true for a record with an entry that is not finite,
-// which is replaced by the identity (sym_funm's rule: the sweeps of a NaN matrix would run to max_iter)
-template <typename T, int N>
-__device__ __forceinline__ bool expand(const T (&r)[sym_k(N)], T (&a)[N][N])
-{
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < sym_k(N); ++k) bad |= !symfun::finite_t(r[k]);
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = 0; j < N; ++j) a[i][j] = bad ? T(i == j) : r[sym_idx(N, i, j)];
-    return bad;
-}
 
 // steps 1 and 2: w = W, lam = L (1 for a bad record), c = C mirrored.  Returns the bad flag: an entry of A or B
 // that is not finite, an eigenvalue of A that is not positive, or a C that is not finite (a base whose
@@ -52,8 +32,8 @@ __device__ __forceinline__ bool whiten(const T (&ra)[sym_k(N)], const T (&rb)[sy
     bool bad;
     {
         T a[N][N], up[N][N];
-        bad = expand<T, N>(ra, a);
-        qr::eig_sym1<T, N, true, true>(a, w, up, lam, N, kMaxIter, kTol);
+        bad = spectral::expand<T, N>(ra, a);
+        qr::eig_sym1<T, N, true, true>(a, w, up, lam, N, spectral::kMaxIter, spectral::kTol);
     } // a and up die here
     bool badb = false;
 #pragma unroll
@@ -68,7 +48,7 @@ __device__ __forceinline__ bool whiten(const T (&ra)[sym_k(N)], const T (&rb)[sy
         for (int i = 0; i < N; ++i) w[i][k] *= rs;
     }
     bad |= badb;
-    // column l of B W, then C_kl for k <= l
+    // column l of B W, then C_kl for k <= l (the congruence of PencilFunBwdOp and SymFunBwdOp without the halving)
     bool badc = false;
 #pragma unroll
     for (int l = 0; l < N; ++l) {
@@ -114,25 +94,6 @@ __device__ __forceinline__ void times_q(T (&m)[N][N], const T (&s)[N], const T (
 #pragma unroll
             for (int k = 1; k < N; ++k) y = qr::fma_t(t[k], q[k][j], y);
             m[i][j] = y;
-        }
-    }
-}
-
-// compact U diag(f) U^T, off-diagonal components times `off` (2 for a gradient); NaN if bad
-template <typename T, int N>
-__device__ __forceinline__ void recompose(const T (&u)[N][N], const T (&f)[N], bool bad, T off, T *o)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        T t[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) t[k] = u[i][k] * f[k];
-#pragma unroll
-        for (int j = i; j < N; ++j) {
-            T y = t[0] * u[j][0];
-#pragma unroll
-            for (int k = 1; k < N; ++k) y = qr::fma_t(t[k], u[j][k], y);
-            o[sym_idx(N, i, j)] = bad ? symfun::nan_t<T>() : (i == j ? y : off * y);
         }
     }
 }

@@ -34,7 +34,7 @@ import ctypes
 from math import sqrt
 import torch
 from . import _lib
-from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, needs_grad, prepare
+from ._dispatch import Batch, broadcast_shapes, expand_batch, launch, max_order, needs_grad, prepare
 
 
 def _nb_prm(K):
@@ -442,16 +442,9 @@ def sym_matmul_solve(j, h, g, eps=None, dtype=None, out=None):
 
 
 # ---------------------------------------------------------------- spectral functions (extension)
-_FUNM_CAPS = {}
-
-
 def _funm_cap(dtype, backward):
     """largest order with a kernel: the compiled table of the library (`nfm_sym_funm_max_order`)"""
-    key = (dtype, bool(backward))
-    if key not in _FUNM_CAPS:
-        from ._dispatch import dtype_code
-        _FUNM_CAPS[key] = int(_lib.lib().nfm_sym_funm_max_order(dtype_code(dtype), int(bool(backward))))
-    return _FUNM_CAPS[key]
+    return max_order('nfm_sym_funm_max_order', dtype, bool(backward))
 
 
 def _funm_args(fn, p, min):
@@ -578,17 +571,12 @@ def sym_clampm(mat, min, dtype=None, out=None):
 
 
 # ---------------------------------------------------------------- two-matrix spectral functions (extension)
-_PENCIL_CAPS = {}
 _PENCIL_FUNS = ('exp', 'log', 'sqrt', 'rsqrt', 'pow')
 
 
 def _pencil_cap(dtype, op):
     """largest order with a kernel: the compiled table of the library (`nfm_sym_pencil_max_order`)"""
-    key = (dtype, op)
-    if key not in _PENCIL_CAPS:
-        from ._dispatch import dtype_code
-        _PENCIL_CAPS[key] = int(_lib.lib().nfm_sym_pencil_max_order(dtype_code(dtype), op))
-    return _PENCIL_CAPS[key]
+    return max_order('nfm_sym_pencil_max_order', dtype, op)
 
 
 def _pencil_order(base, mat):

@@ -15,7 +15,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nitorch_fastmath_amd import _lib  # noqa: E402
 from nitorch_fastmath_amd._dispatch import stream_ptr  # noqa: E402
-from _timing import timeit  # noqa: E402
+from _timing import BUILDS_HEADER, builds_row as row, load_build  # noqa: E402
 
 dev = torch.device('cuda:0')
 Q8 = [0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999]          # bench_quantile.py
@@ -24,14 +24,8 @@ MEDIAN = {torch.float32: ((1, 1 << 30), (64, 1 << 24), (1 << 14, 1 << 16)),
 QUANTILE = ((1, 1 << 28), (64, 1 << 24), (1 << 14, 1 << 16))   # bench_quantile.py, rows longer than 1024
 
 
-def load(path):
-    L = ctypes.CDLL(os.path.abspath(path))
-    for name in ('nfm_reduce_median', 'nfm_reduce_quantile', 'nfm_reduce_median_workspace_bytes',
-                 'nfm_reduce_quantile_workspace_bytes'):
-        fn = getattr(L, name)
-        fn.argtypes = _lib.SIGNATURES[name]
-        fn.restype = ctypes.c_size_t if name.endswith('_workspace_bytes') else ctypes.c_int
-    return L
+ENTRIES = ('nfm_reduce_median', 'nfm_reduce_quantile', 'nfm_reduce_median_workspace_bytes',
+           'nfm_reduce_quantile_workspace_bytes')
 
 
 def median_call(L, x, ws, val, st):
@@ -55,26 +49,10 @@ def quantile_call(L, x, interp, qs, ws, val, st):
     return fn
 
 
-def row(name, parent, branch, val):
-    """parent, branch, parent on the same buffers; the branch's result against the first parent's"""
-    times, kept = [], []
-    for fn in (parent, branch, parent):
-        times.append(timeit(fn, reps=24) * 1e3)
-        torch.cuda.synchronize()
-        kept.append(val.clone())
-    same = torch.equal(kept[0].view(torch.uint8), kept[1].view(torch.uint8))
-    p1, b, p2 = times
-    spread, ratio = max(p1, p2) / min(p1, p2), b / min(p1, p2)
-    print(f'| {name} | {p1:.4f} | {b:.4f} | {p2:.4f} | {spread:.4f} | {ratio:.4f} | {"yes" if ratio <= spread else "no"} | '
-          f'{"yes" if same else "NO"} |', flush=True)
-
-
 def main():
-    P, B = load(sys.argv[1]), load(sys.argv[2])
+    P, B = load_build(sys.argv[1], ENTRIES), load_build(sys.argv[2], ENTRIES)
     st = stream_ptr(dev)
-    print('| call | parent ms | branch ms | parent again ms | parent slower / faster | branch / faster parent | within '
-          '| same bits |')
-    print('|---|---|---|---|---|---|---|---|')
+    print(BUILDS_HEADER)
     for dtype in (torch.float32, torch.float64):
         dn = str(dtype)[6:]
         for rows, red in MEDIAN[dtype]:
