@@ -95,7 +95,7 @@ struct HessOp {
         T a[N][N], up[N][N];
         if constexpr (SYM) {
             to_mat<T, N>(r, a, p.upper);
-            qr::hessenberg_sym1<T, N, WITH_U>(a, N, up);
+            qr::hessenberg_sym1<T, N, WITH_U, false, false, true, true>(a, N, up);
         } else {
             to_mat<T, N>(r, a, -1);
             qr::hessenberg1<T, N, WITH_U>(a, N, up);
@@ -185,7 +185,7 @@ struct HouseholderOp {
         T u[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) u[i] = x[i];
-        const T alpha = qr::householder1<T, N>(u, N, p.basis);
+        const T alpha = qr::householder1<T, N, false, false, true>(u, N, p.basis);
 #pragma unroll
         for (int i = 0; i < N; ++i) o[i] = u[i];
         o[N] = alpha;
@@ -203,7 +203,7 @@ struct GivensOp {
     static __device__ __forceinline__ void apply(const T (&x)[1], const T (&y)[1], const T (&)[1], T (&o)[2],
                                                  const Params &)
     {
-        qr::givens1(x[0], y[0], o[0], o[1]);
+        qr::givens_guard1<T>(x[0], y[0], o[0], o[1]);
     }
 };
 
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(LANES) void qr_lds_kernel(Opnd a, Opnd b, T *__rest
         T x[MX];
 #pragma unroll
         for (int r = 0; r < MX; ++r) x[r] = (r < n) ? pa[r * a.sc] : T(0);
-        const T alpha = qr::householder1<T, 0>(x, n, p.basis);
+        const T alpha = qr::householder1<T, 0, false, false, true>(x, n, p.basis);
 #pragma unroll
         for (int r = 0; r < MX; ++r)
             if (r < n) po[r] = x[r];
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(LANES) void qr_lds_kernel(Opnd a, Opnd b, T *__rest
         // the tridiagonal result is written out symmetric from its lower half; the upper half of the image
         // holds the reflectors (FILL = false)
         qr::UpperRows<T, M> up{m};
-        qr::hessenberg_sym1<T, 0, OP == QG_HESSSYM_U, false, false, false>(m, n, up);
+        qr::hessenberg_sym1<T, 0, OP == QG_HESSSYM_U, false, false, false, true>(m, n, up);
         for (int r = 0; r < n; ++r)
             for (int c = 0; c < n; ++c) po[r * n + c] = r >= c ? m[r][c] : m[c][r];
         if (OP == QG_HESSSYM_U)
@@ -427,7 +427,9 @@ NFM_QR_LDS_DECL(f64, 0) NFM_QR_LDS_DECL(f64, 1) NFM_QR_LDS_DECL(f64, 2) NFM_QR_L
 // lane, which costs a move each way but no memory).  Everything else runs from LDS (qr_lds_kernel).
 // largest order without a private segment, per case (f32: everything else fits at every order)
 constexpr int NFM_QRL_F32_HESSU_MAX = 15, NFM_QRL_F32_QR_MAX = 16, NFM_QRL_F32_EIGU_MAX = 10, NFM_QRL_F32_EIGUF_MAX = 11, NFM_QRL_F32_RQU_MAX = 11;
-constexpr int NFM_QRL_F64_EIG_MAX = 15, NFM_QRL_F64_EIGF_MAX = 15, NFM_QRL_F64_HESS_MAX = 11, NFM_QRL_F64_HSYM_MAX = 15,
+// (hessenberg_sym at order 15: with reflectors it fits, without them the range guard's vote costs a 56-byte private
+// segment: profiles/qr_family_register_fit.txt, the survey repeated with the guard)
+constexpr int NFM_QRL_F64_EIG_MAX = 15, NFM_QRL_F64_EIGF_MAX = 15, NFM_QRL_F64_HESS_MAX = 11, NFM_QRL_F64_HSYM_MAX = 14, NFM_QRL_F64_HSYMU_MAX = 15,
               NFM_QRL_F64_QR_MAX = 11, NFM_QRL_F64_RQ_MAX = 13, NFM_QRL_F64_EIGU_MAX = 10, NFM_QRL_F64_EIGUF_MAX = 9,
               NFM_QRL_F64_RQU_MAX = 8;
 constexpr bool qr_large_fits(bool f64, int N, int op)
@@ -449,7 +451,8 @@ constexpr bool qr_large_fits(bool f64, int N, int op)
     case QG_EIG: return N <= NFM_QRL_F64_EIG_MAX;
     case QG_EIG_FAST: return N <= NFM_QRL_F64_EIGF_MAX;
     case QG_HESS: case QG_HESS_U: return N <= NFM_QRL_F64_HESS_MAX;
-    case QG_HESSSYM: case QG_HESSSYM_U: return N <= NFM_QRL_F64_HSYM_MAX;
+    case QG_HESSSYM: return N <= NFM_QRL_F64_HSYM_MAX;
+    case QG_HESSSYM_U: return N <= NFM_QRL_F64_HSYMU_MAX;
     case QG_QR: return N <= NFM_QRL_F64_QR_MAX;
     case QG_RQ: return N <= NFM_QRL_F64_RQ_MAX;
     case QG_EIG_U: return N <= NFM_QRL_F64_EIGU_MAX;

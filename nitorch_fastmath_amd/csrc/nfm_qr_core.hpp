@@ -135,6 +135,41 @@ template <>
 struct FastRange<double> {
     static constexpr double lo = 0x1p-900, hi = 0x1p900;
 };
+__device__ __forceinline__ float ldexp_t(float x, int k) { return __builtin_ldexpf(x, k); }
+__device__ __forceinline__ double ldexp_t(double x, int k) { return __builtin_ldexp(x, k); }
+// exponent e of mx > 0 (mx in [2^e, 2^(e+1)), subnormals included)
+__device__ __forceinline__ int exponent_of(float mx)
+{
+    const unsigned b = __builtin_bit_cast(unsigned, mx);
+    const int E = (int)(b >> 23);
+    return E ? E - 127 : (31 - __builtin_clz(b | 1u)) - 149;
+}
+__device__ __forceinline__ int exponent_of(double mx)
+{
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, mx);
+    const int E = (int)(b >> 52);
+    return E ? E - 1023 : (63 - __builtin_clzll(b | 1ull)) - 1074;
+}
+
+// ---------------------------------------------------------------------------------------
+// Range guard of the PUBLIC building blocks (givens, householder, hessenberg, hessenberg_sym, qr_hessenberg,
+// rq_hessenberg).  Upstream normalises a rotation and a reflector by an unscaled sum of
+// squares.  For a pair or a column below about 2^-63 (float64: 2^-511) inside a record of any scale -- rank-deficient
+// records, rows that are tiny next to the others -- the squares are subnormal or zero (or they overflow), the "unit"
+// vector is not of unit length, and the reflection I - 2 u u^T is then applied to the O(1) part of the record as well.
+// The guard's window [FastRange::lo, FastRange::hi] = [2^-100, 2^100] (float64: 2^+-900) keeps a margin above that
+// onset: entries of about 2^-50 / 2^-450.  GUARD = true: a lane whose
+// sum of squares is outside the window takes the scaled form instead -- the rotation of the pair divided by its
+// larger magnitude (givens_scaled1), the reflector of the vector times the exact power of two that brings its
+// largest magnitude into [1, 2), alpha scaled back (one rounding, only where it is subnormal).  The scaled form
+// runs on a wavefront vote and its result is taken by the voting lanes only: inside the window the bits are
+// those of the unguarded form.  The CPU restatement carries the same guard, bit for bit.
+// eig_sym's reference-order sweeps stay unguarded (they reproduce upstream; tests/_eig_ref.py REFERENCE_EXCEEDS).
+template <typename T>
+__device__ __forceinline__ bool sq_in_window(T ss)
+{
+    return ss >= FastRange<T>::lo && ss <= FastRange<T>::hi; // NaN: outside
+}
 
 // ---------------------------------------------------------------------------------------
 // Correctly rounded division and square root WITHOUT their range handling: what eig_sym's
@@ -314,6 +349,22 @@ __device__ __forceinline__ void givens1(T x, T y, T &c, T &s)
     s = z ? T(0) : -(y / nrm);
 }
 
+// givens1 of the public entry points (range guard above): lanes whose x^2 + y^2 is outside the window take
+// givens_scaled1 on a wavefront vote, the others keep givens1's bits
+template <typename T>
+__device__ __forceinline__ void givens_guard1(T x, T y, T &c, T &s)
+{
+#pragma clang fp contract(off)
+    const bool ok = sq_in_window(x * x + y * y);
+    givens1<T>(x, y, c, s);
+    if (__builtin_expect(__any(!ok), 0)) {
+        T c2, s2;
+        givens_scaled1<T>(x, y, c2, s2);
+        c = ok ? c : c2;
+        s = ok ? s : s2;
+    }
+}
+
 // tmp = s*a0; a0 = a0*c - s*a1; a1 = a1*c + tmp   (_givens_apply_* :370-402)
 template <typename T>
 __device__ __forceinline__ void rot1(T &a0, T &a1, T c, T s)
@@ -373,10 +424,13 @@ __device__ __forceinline__ void rot_pair1(T &a0, T &a1, T c, T s)
 // the element is picked by a select so that registers are never indexed dynamically)
 // TRIM (eig_sym's reference-order arithmetic): the two square roots and the m divisions run the trimmed
 // correctly rounded sequences (CrRange above) when every active lane is in range -- the same bits
-template <typename T, int NT, bool FAST = false, bool TRIM = false>
+// GUARD (the public entry points; range guard above): a lane whose sum of squares is outside the window works on
+// x 2^k, k the exact power of two that brings its largest magnitude into [1, 2), and returns alpha 2^-k
+template <typename T, int NT, bool FAST = false, bool TRIM = false, bool GUARD = false>
 __device__ __forceinline__ T householder1(T (&x)[Dim<NT>::MAX], int m, int basis)
 {
 #pragma clang fp contract(off)
+    static_assert(!(GUARD && (FAST || TRIM)), "the guard belongs to the public building blocks");
     T xb = T(0);
 #pragma unroll
     for (int i = 0; i < Dim<NT>::MAX; ++i)
@@ -388,6 +442,26 @@ __device__ __forceinline__ T householder1(T (&x)[Dim<NT>::MAX], int m, int basis
 #pragma unroll
     for (int i = 0; i < Dim<NT>::MAX; ++i)
         if (i < m) ss += x[i] * x[i];
+    [[maybe_unused]] int back = 0; // alpha is returned times 2^back
+    if constexpr (GUARD) {
+        const bool ok = sq_in_window(ss);
+        if (__builtin_expect(__any(!ok), 0)) {
+            T big = T(0);
+#pragma unroll
+            for (int i = 0; i < Dim<NT>::MAX; ++i)
+                if (i < m) big = fabs_(x[i]) > big ? fabs_(x[i]) : big;
+            // zero vectors, inf: as they are (NaN is never the maximum); lanes inside the window: 2^0, the identity
+            const int k = (!ok && big > T(0) && finite_(big)) ? -exponent_of(big) : 0;
+#pragma unroll
+            for (int i = 0; i < Dim<NT>::MAX; ++i)
+                if (i < m) x[i] = ldexp_t(x[i], k);
+            ss = T(0);
+#pragma unroll
+            for (int i = 0; i < Dim<NT>::MAX; ++i)
+                if (i < m) ss += x[i] * x[i];
+            back = -k;
+        }
+    }
     if constexpr (FAST) {
         // eig_sym's fast arithmetic (policy above): |x| = ss rsqrt(ss); the reflected component is
         // x_b - rho = sgn(x_b) (|x_b| + |x|), so the squared norm of the un-normalised reflector is
@@ -464,6 +538,7 @@ __device__ __forceinline__ T householder1(T (&x)[Dim<NT>::MAX], int m, int basis
             const T v = x[i] / nrm;
             x[i] = finite_(v) ? v : T(0);
         }
+    if constexpr (GUARD) return ldexp_t(rho, back);
     return rho;
 }
 
@@ -481,7 +556,7 @@ __device__ __forceinline__ void hessenberg1(MA &a, int n, MU &up)
 #pragma unroll
             for (int r = 0; r < MX; ++r)
                 if (r < m) u[r] = a[k + 1 + r][k];
-            const T alpha = householder1<T, NT>(u, m, 0);
+            const T alpha = householder1<T, NT, false, false, true>(u, m, 0);
             if (WITH_U) {
 #pragma unroll
                 for (int r = 0; r < MX; ++r)
@@ -522,7 +597,9 @@ __device__ __forceinline__ void hessenberg1(MA &a, int n, MU &up)
 // view does for upper=True).  Output: symmetric tridiagonal, both halves filled.
 // FILL = false (eig_sym): the upper triangle is left alone (the sweeps run on the band d, e taken from the
 // lower half, and the LDS form keeps the reflectors there)
-template <typename T, int NT, bool WITH_U, bool FAST = false, bool TRIM = false, bool FILL = true, class MA, class MU>
+// GUARD: the range guard of householder1 (the public hessenberg_sym; eig_sym passes false)
+template <typename T, int NT, bool WITH_U, bool FAST = false, bool TRIM = false, bool FILL = true, bool GUARD = false,
+          class MA, class MU>
 __device__ __forceinline__ void hessenberg_sym1(MA &a, int n, MU &up)
 {
 #pragma clang fp contract(off)
@@ -535,7 +612,7 @@ __device__ __forceinline__ void hessenberg_sym1(MA &a, int n, MU &up)
 #pragma unroll
             for (int r = 0; r < MX; ++r)
                 if (r < m) u[r] = a[o + r][k];
-            const T alpha = householder1<T, NT, FAST, TRIM>(u, m, 0);
+            const T alpha = householder1<T, NT, FAST, TRIM, GUARD>(u, m, 0);
             if (WITH_U) {
 #pragma unroll
                 for (int r = 0; r < MX; ++r)
@@ -621,7 +698,7 @@ __device__ __forceinline__ void qr_hessenberg1(MA &a, MQ &q, int n)
     for (int k = 0; k < MX - 1; ++k) {
         if (k < n - 1) {
             T c, s;
-            givens1(a[k][k], a[k + 1][k], c, s);
+            givens_guard1<T>(a[k][k], a[k + 1][k], c, s);
 #pragma unroll
             for (int j = k; j < MX; ++j)
                 if (j < n) rot1(a[k][j], a[k + 1][j], c, s);
@@ -641,7 +718,7 @@ __device__ __forceinline__ void rq_step1(MA &a, MU &u, int n, int m, bool sym)
     T lc[MX], ls[MX];
     auto giv = [](T x, T y, T &c, T &s) {
         if constexpr (FM) givens_fast1(x, y, c, s);
-        else givens1(x, y, c, s);
+        else givens_guard1(x, y, c, s); // (FM = false is the public rq_hessenberg only: range guard above)
     };
     auto rot = [](T &a0, T &a1, T c, T s) {
         if constexpr (FM) rot_fast1(a0, a1, c, s);
@@ -1099,8 +1176,6 @@ template <>
 struct EigWindow<double> {
     static constexpr int lo = -480, hi = 480;
 };
-__device__ __forceinline__ float ldexp_t(float x, int k) { return __builtin_ldexpf(x, k); }
-__device__ __forceinline__ double ldexp_t(double x, int k) { return __builtin_ldexp(x, k); }
 // the (high) dword of |x|: sign off, exponent field on top -- ordered like |x| itself as an unsigned integer, and
 // all that the window test needs (NaN sorts above inf)
 __device__ __forceinline__ unsigned abs_hi(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
@@ -1122,19 +1197,6 @@ struct EigBits<double> {
     static constexpr unsigned hi = ((unsigned)(EigWindow<double>::hi + 1024) << 20) - 1u;
     static constexpr unsigned inf = 0x7ff00000u;
 };
-// exponent e of mx > 0 (mx in [2^e, 2^(e+1)), subnormals included)
-__device__ __forceinline__ int exponent_of(float mx)
-{
-    const unsigned b = __builtin_bit_cast(unsigned, mx);
-    const int E = (int)(b >> 23);
-    return E ? E - 127 : (31 - __builtin_clz(b | 1u)) - 149;
-}
-__device__ __forceinline__ int exponent_of(double mx)
-{
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, mx);
-    const int E = (int)(b >> 52);
-    return E ? E - 1023 : (63 - __builtin_clzll(b | 1ull)) - 1074;
-}
 // visit the lower triangle (diagonal included) of the leading n x n block: f(a[i][j]).  Compile-time orders
 // recurse over a literal linear index instead of looping: the visits sit inside a uniform branch, where a loop nest
 // is unrolled too late for the register matrix to be split into scalars (it went to scratch memory).

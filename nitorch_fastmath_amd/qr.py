@@ -10,7 +10,7 @@ each matrix lives in the registers of one lane and iterates until ITS OWN conver
 (`_impl/qr.py:640-653`'s criterion, applied per matrix), one kernel launch per call.
 
 Real dtypes (float32 / float64) only.  Deliberate deviations from upstream, all bug fixes
-(SURVEY quirks Q7-Q9): `eig_sym`/`hessenberg_sym` work for every order <= 16 (upstream
+(SURVEY quirks Q7-Q9c): `eig_sym`/`hessenberg_sym` work for every order <= 16 (upstream
 raises for batched n > 5); `rq_hessenberg` returns the true R Q for any Hessenberg input
 (upstream is only right for tridiagonal input or n <= 3); eigenvalues come in each matrix's
 own deflation order, i.e. what upstream returns when called on that matrix alone (its order
@@ -34,7 +34,16 @@ its range.  `eig_sym` (both modes) therefore scales a record whose largest entry
 is read, lies outside [2^-50, 2^57) (float64: [2^-480, 2^481)) by the exact power of two that brings that
 entry into [1, 2), and scales the eigenvalues back (one rounding, only where the result is subnormal);
 inside the window nothing changes, bit for bit.  Every finite input, subnormal ones included, is solved to
-a few n eps |A|_2 per record (tests/_eig_ref.py).  The other entry points of this module keep upstream's range.
+a few n eps |A|_2 per record (tests/_eig_ref.py).
+The building blocks (`givens`, `householder`, `hessenberg`, `hessenberg_sym`, `qr_hessenberg`, `rq_hessenberg`) do not
+scale records; they guard each normalisation instead.  Upstream divides a rotation and a reflector by
+an unscaled sum of squares, which is subnormal or zero for a pair or a column below about 2^-63 (float64: 2^-511) -- a
+rank-deficient record, rows that are tiny next to the others -- so that the "unit" vector is not of unit length (off by
+per cents) and `I - 2 u u^T` then damages the O(1) part of the record.  Where that sum leaves [2^-100, 2^100]
+(float64: [2^-900, 2^900]; entries of about 2^-50 / 2^-450, a margin above the onset) the rotation is formed from the pair divided by its larger magnitude and the reflector from
+the vector times an exact power of two, `alpha` scaled back; inside the window nothing changes, bit for bit.  Every
+finite input whose results are representable is held to 16 n eps per record (tests/_qr_ref.py,
+profiles/qr_family_accuracy.md).
 
 Hard spectra.  `'reference'` is upstream's arithmetic, with its limits: `tol = 1e-32` is out of float32's
 reach on repeated or clustered eigenvalues (those stages run all `max_iter` sweeps) and its rotations

@@ -6,7 +6,8 @@
  * unspecified).  Deviations from the reference, all deliberate (SURVEY quirks):
  *   Q7  matvec_sym for n > 4 raises upstream for batched input -> the intended product;
  *   Q8  rq_hessenberg column rotations cover rows 0..k+1 (true R Q) unless `sym`;
- *   Q9  convergence is judged per matrix, with the reference's criterion. */
+ *   Q9  convergence is judged per matrix, with the reference's criterion;
+ *   Q9c the public building blocks (everything but eig_sym) guard the range of their sums of squares. */
 
 /* _givens_jit :326-334 */
 static inline void FN(givens1)(T x, T y, T *c, T *s)
@@ -15,6 +16,34 @@ static inline void FN(givens1)(T x, T y, T *c, T *s)
     if (nrm == (T)0) { *c = (T)1; *s = (T)0; return; }
     *c = x / nrm;
     *s = -(y / nrm);
+}
+
+/* The range guard of the public building blocks (Q9c; shared bit for bit with nfm_qr_core.hpp `sq_in_window`,
+ * `givens_guard1`, `householder1<.., GUARD>`).  Upstream normalises by an unscaled sum of squares; outside this
+ * window the squares are subnormal or zero (or overflow) and the "unit" vector is not of unit length.  A pair or a
+ * vector outside it takes the scaled form; inside it nothing changes, bit for bit.  eig_sym stays unguarded. */
+static inline int FN(sq_in_window)(T ss)
+{
+    const double lo = sizeof(T) == 4 ? 0x1p-100 : 0x1p-900, hi = sizeof(T) == 4 ? 0x1p100 : 0x1p900;
+    return (double)ss >= lo && (double)ss <= hi; /* NaN: outside */
+}
+
+/* givens1 on the pair divided by its larger magnitude (one component becomes +-1 exactly) */
+static inline void FN(givens_scaled1)(T x, T y, T *c, T *s)
+{
+    T ax = FABS(x), ay = FABS(y);
+    T m = ax > ay ? ax : ay;
+    if (m == (T)0) { *c = (T)1; *s = (T)0; return; }
+    T xs = x / m, ys = y / m;
+    T nrm = SQRT(xs * xs + ys * ys);
+    *c = xs / nrm;
+    *s = -(ys / nrm);
+}
+
+static inline void FN(givens_guard1)(T x, T y, T *c, T *s)
+{
+    if (FN(sq_in_window)(x * x + y * y)) FN(givens1)(x, y, c, s);
+    else FN(givens_scaled1)(x, y, c, s);
 }
 
 /* rotate the pair (p0[k*st], p1[k*st]), k < len : _givens_apply_* :370-402
@@ -50,6 +79,24 @@ static inline T FN(householder1)(int m, T *x, int basis)
     return rho;
 }
 
+/* householder1 with the range guard: a vector whose sum of squares is outside the window is reflected as
+ * x 2^-e, e the exponent of its largest magnitude (exact), and alpha is scaled back (one rounding, only where
+ * it is subnormal).  Zero vectors and vectors with an inf or a NaN go through as they are. */
+static inline T FN(householder_guard1)(int m, T *x, int basis)
+{
+    T ss = (T)0, big = (T)0;
+    for (int i = 0; i < m; ++i) ss += x[i] * x[i];
+    if (FN(sq_in_window)(ss)) return FN(householder1)(m, x, basis);
+    for (int i = 0; i < m; ++i) { T v = FABS(x[i]); big = (v > big) ? v : big; }
+    if (!(big > (T)0) || !ISFINITE(big)) return FN(householder1)(m, x, basis);
+    int e;
+    (void)frexp((double)big, &e);
+    e -= 1; /* big in [2^e, 2^(e+1)) */
+    for (int i = 0; i < m; ++i) x[i] = (T)ldexp((double)x[i], -e);
+    T rho = FN(householder1)(m, x, basis);
+    return (T)ldexp((double)rho, e);
+}
+
 /* apply P = I - 2 u u^T (u of length m) to the trailing rows / columns of the N x N matrix a
  * householder_apply_ :72-106 */
 static inline void FN(householder_apply1)(int N, int m, T *a, const T *u, int left, int right)
@@ -78,7 +125,7 @@ static inline void FN(hessenberg1)(int N, T *a, T *upack)
     for (int k = 0; k < N - 2; ++k) {
         const int m = N - k - 1;
         for (int r = 0; r < m; ++r) u[r] = a[(k + 1 + r) * N + k];
-        T alpha = FN(householder1)(m, u, 0);
+        T alpha = FN(householder_guard1)(m, u, 0);
         if (upack) for (int r = 0; r < m; ++r) upack[k * (N - 1) + r] = u[r];
         /* left: a[k+1:, k+1:] -= 2 u (u^T a[k+1:, k+1:]) */
         for (int c = k + 1; c < N; ++c) {
@@ -98,15 +145,16 @@ static inline void FN(hessenberg1)(int N, T *a, T *upack)
 }
 
 /* hessenberg_sym_lower_ :296-323 (reads/updates the LOWER triangle only); with upper != 0 the
- * same algorithm runs on the transpose (hessenberg_sym_upper_ :280-293).  fill: mirror. */
-static inline void FN(hessenberg_sym1)(int N, T *a, int upper, int fill, T *upack)
+ * same algorithm runs on the transpose (hessenberg_sym_upper_ :280-293).  fill: mirror.
+ * guard: the range guard of the reflectors (the public entry point; eig_sym passes 0). */
+static inline void FN(hessenberg_sym1)(int N, T *a, int upper, int fill, T *upack, int guard)
 {
 #define L_(i, j) (upper ? a[(j) * N + (i)] : a[(i) * N + (j)]) /* element (i,j) of the lower view */
     T u[NFM_MAXM], v[NFM_MAXM];
     for (int k = 0; k < N - 2; ++k) {
         const int m = N - k - 1, o = k + 1;
         for (int r = 0; r < m; ++r) u[r] = L_(o + r, k);
-        T alpha = FN(householder1)(m, u, 0);
+        T alpha = guard ? FN(householder_guard1)(m, u, 0) : FN(householder1)(m, u, 0);
         if (upack) for (int r = 0; r < m; ++r) upack[k * (N - 1) + r] = u[r];
         /* v = A_k u using the lower triangle (matvec_sym :201-237) */
         for (int i = 0; i < m; ++i) {
@@ -141,19 +189,21 @@ static inline void FN(qr_hessenberg1)(int N, T *a, T *q)
     for (int i = 0; i < N; ++i) q[i * N + i] = (T)1;
     for (int k = 0; k < N - 1; ++k) {
         T c, s;
-        FN(givens1)(a[k * N + k], a[(k + 1) * N + k], &c, &s);
+        FN(givens_guard1)(a[k * N + k], a[(k + 1) * N + k], &c, &s);
         FN(rot)(a + k * N + k, a + (k + 1) * N + k, 1, N - k, c, s);  /* rows k, k+1, columns k: */
         FN(rot)(q + k, q + k + 1, N, k + 2, c, s);                    /* columns k, k+1, rows :k+2 */
     }
 }
 
 /* one RQ step on the leading m x m block of the N x N matrix a (and column rotations of
- * the N-row matrix u, ncols = m): _rq_hessenberg(_vectors)_jit_ :457-522 */
-static inline void FN(rq_step)(int N, int m, T *a, T *u, int sym, int true_rq)
+ * the N-row matrix u, ncols = m): _rq_hessenberg(_vectors)_jit_ :457-522
+ * guard: the range guard of the rotations (the public entry point; eig_sym's sweeps pass 0) */
+static inline void FN(rq_step)(int N, int m, T *a, T *u, int sym, int true_rq, int guard)
 {
     T lc[NFM_MAXM], ls[NFM_MAXM];
     for (int k = 0; k < m - 1; ++k) {
-        FN(givens1)(a[k * N + k], a[(k + 1) * N + k], &lc[k], &ls[k]);
+        if (guard) FN(givens_guard1)(a[k * N + k], a[(k + 1) * N + k], &lc[k], &ls[k]);
+        else FN(givens1)(a[k * N + k], a[(k + 1) * N + k], &lc[k], &ls[k]);
         int len = sym ? (k + 3 <= m ? 3 : m - k) : m - k;
         FN(rot)(a + k * N + k, a + (k + 1) * N + k, 1, len, lc[k], ls[k]);
     }
@@ -191,7 +241,7 @@ static inline void FN(qr_explicit1)(int N, T *h, T *u, int max_iter, double tol,
             if (sweeps) sweeps[m - 1] += 1;
             T sigma = FN(wilkinson1)(N, m, h);
             for (int i = 0; i < m; ++i) h[i * N + i] -= sigma;
-            FN(rq_step)(N, m, h, u, 1, 0);
+            FN(rq_step)(N, m, h, u, 1, 0, 0);
             for (int i = 0; i < m; ++i) h[i * N + i] += sigma;
             T bb = FABS(h[(m - 1) * N + (m - 2)]), a0 = FABS(h[(m - 1) * N + (m - 1)]);
             T a1 = FABS(h[(m - 2) * N + (m - 2)]);
@@ -251,7 +301,7 @@ static inline void FN(eig_sym1)(int N, T *a, int upper, int compute_u, int max_i
 {
     T upack[NFM_MAXM * NFM_MAXM];
     const int shift = FN(eig_prescale1)(N, a, upper);
-    FN(hessenberg_sym1)(N, a, upper, 1, compute_u ? upack : NULL);
+    FN(hessenberg_sym1)(N, a, upper, 1, compute_u ? upack : NULL, 0);
     FN(qr_explicit1)(N, a, compute_u ? vecs : NULL, max_iter, tol, sweeps);
     if (compute_u) /* householder_apply_(u, q, side='left', inverse=True): reflectors in reverse */
         for (int k = N - 3; k >= 0; --k) FN(householder_apply1)(N, N - k - 1, vecs, upack + k * (N - 1), 1, 0);
@@ -264,7 +314,7 @@ static inline void FN(eig_sym1)(int N, T *a, int upper, int compute_u, int max_i
 static int FN(nfm_oracle_qr_givens)(int64_t n, const T *x, const T *y, T *c, T *s)
 {
 #pragma omp parallel for schedule(static)
-    for (int64_t b = 0; b < n; ++b) FN(givens1)(x[b], y[b], &c[b], &s[b]);
+    for (int64_t b = 0; b < n; ++b) FN(givens_guard1)(x[b], y[b], &c[b], &s[b]);
     return 0;
 }
 
@@ -285,7 +335,7 @@ static int FN(nfm_oracle_qr_givens_apply)(int N, int64_t n, int side, int i, int
 static int FN(nfm_oracle_qr_householder)(int N, int64_t n, int basis, T *x, T *alpha)
 {
 #pragma omp parallel for schedule(static)
-    for (int64_t b = 0; b < n; ++b) alpha[b] = FN(householder1)(N, x + b * N, basis);
+    for (int64_t b = 0; b < n; ++b) alpha[b] = FN(householder_guard1)(N, x + b * N, basis);
     return 0;
 }
 
@@ -310,7 +360,7 @@ static int FN(nfm_oracle_qr_hessenberg_sym)(int N, int64_t n, int upper, int fil
     const int us = (N - 2 > 0 ? N - 2 : 0) * (N - 1);
 #pragma omp parallel for schedule(static)
     for (int64_t b = 0; b < n; ++b)
-        FN(hessenberg_sym1)(N, a + b * N * N, upper, fill, upack ? upack + b * us : NULL);
+        FN(hessenberg_sym1)(N, a + b * N * N, upper, fill, upack ? upack + b * us : NULL, 1);
     return 0;
 }
 
@@ -324,7 +374,7 @@ static int FN(nfm_oracle_qr_qr_hessenberg)(int N, int64_t n, T *a, T *q)
 static int FN(nfm_oracle_qr_rq_hessenberg)(int N, int64_t n, int sym, int true_rq, T *a, T *u)
 {
 #pragma omp parallel for schedule(static)
-    for (int64_t b = 0; b < n; ++b) FN(rq_step)(N, N, a + b * N * N, u ? u + b * N * N : NULL, sym, true_rq);
+    for (int64_t b = 0; b < n; ++b) FN(rq_step)(N, N, a + b * N * N, u ? u + b * N * N : NULL, sym, true_rq, 1);
     return 0;
 }
 
