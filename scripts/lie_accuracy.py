@@ -3,8 +3,11 @@
 per (dtype, D) the worst error max|K - T| / max|T| of the kernel and of the reference, and the worst ratio
 err / (D eps (1 + ||X||_1)) -- the constant C of the test bound C D eps (1 + ||X||_1).  The Frechet kernels get the
 same per input class of tests/_lie_ref.py: float32 at D = 1..4 and both depths, float64 on tests/golden/lie_frechet.npz.
+The forward kernels by input class (`--forward`: that section alone): the interleaved batches of
+tests/test_gpu_lie_forward.py in units of D eps max(1, cond_exp(X)) on the Frobenius error; without a GPU the kernel
+cells say "not measured".
 
-    python scripts/lie_accuracy.py [--md out.md]"""
+    python scripts/lie_accuracy.py [--md out.md] [--forward]"""
 import argparse
 import os
 import sys
@@ -16,10 +19,43 @@ sys.path.insert(0, ROOT)
 import nitorch_fastmath_amd as N  # noqa: E402
 
 
+def forward_section():
+    """worst ||K - T||_F / (||T||_F D eps max(1, cond_exp)) per (dtype, order, class): the kernel, the float model of
+    its formulas (tests/_lie_ref.expm_model) and torch.linalg.matrix_exp in the same dtype on the CPU"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import _lie_ref as R
+    from nitorch_fastmath_amd import lie
+    gpu = torch.cuda.is_available()
+    out = ['', '| forward kernels | D | class | records | kernel worst C | model worst C | matrix_exp worst C | worst cond_exp |',
+           '|---|---|---|---|---|---|---|---|']
+    for dn in ('f32', 'f64'):
+        dtype = R.DT[dn]
+        for D in range(1, lie.FORWARD_MAX[dtype] + 1):
+            x, idx, t, cond = R.fwd_case(D, dn)
+            classes = R.fwd_classes(dn, D)
+            cm = R.fwd_worst(R.fwd_c(R.expm_model(x, dtype)[0], t, x, dtype, cond), idx, classes)
+            cr = R.fwd_worst(R.fwd_c(torch.linalg.matrix_exp(x) if D > 1 else torch.exp(x), t, x, dtype, cond), idx, classes)
+            ck = R.fwd_worst(R.fwd_c(lie.expm(x.cuda()).cpu(), t, x, dtype, cond), idx, classes) if gpu else None
+            wc = R.fwd_worst(cond, idx, classes)
+            for q, cls in enumerate(classes):
+                name = R.cname(cls)
+                kernel = f'{ck[name]:.2f}' if gpu else 'not measured'
+                out.append(f'| {dn} | {D} | {name} | {int((idx == q).sum())} | {kernel} | {cm[name]:.2f} | {cr[name]:.2f} | '
+                           f'{wc[name]:.3g} |')
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--md')
+    ap.add_argument('--forward', action='store_true', help='the forward-kernels-by-class section alone')
     args = ap.parse_args()
+    if args.forward:
+        out = '\n'.join(forward_section()[1:]) + '\n'
+        print(out)
+        if args.md:
+            open(args.md, 'w').write(out)
+        return
     g = np.load(os.path.join(ROOT, 'tests', 'golden', 'lie.npz'))
     lines = ['| dtype | D | kernel worst err | reference worst err | kernel worst C | reference worst C (finite) |',
              '|---|---|---|---|---|---|']
@@ -89,7 +125,7 @@ def main():
             err = (N.lie.expm(x).double() - t).abs().amax((-2, -1)) / t.abs().amax((-2, -1))
             c = err / (D * torch.finfo(dtype).eps * (1 + x.double().abs().sum(-2).amax(-1)))
             sl.append(f'| {str(dtype)[6:]} | {D} | {float(err.max()):.2e} | {float(c.max()):.2f} |')
-    out = '\n'.join(lines + dl + fl + sl + ['', f'worst C on the fixture: expm {worst:.2f}, derivatives {worst_d:.2f}']) + '\n'
+    out = '\n'.join(lines + dl + fl + forward_section() + sl + ['', f'worst C on the fixture: expm {worst:.2f}, derivatives {worst_d:.2f}']) + '\n'
     print(out)
     if args.md:
         open(args.md, 'w').write(out)

@@ -9,6 +9,10 @@ test_gpu_lie_derivatives.py).  Plain torch on the CPU; nothing here touches the 
     frechet_model     a transcription of the algorithm in the header of nfm_lie_ops.hpp (scaling, degree, three
                       coupled Horner recurrences, squarings): shows that the bars are attainable and gives the value
                       of a truncated series.  A model of the formulas, not of the fma order: nothing is held to its bits.
+    expm_model        the forward part of that transcription, E alone: the same for `ExpmOp`
+
+The forward kernels have classes, a conditioning unit (`cond_exp`, `fwd_unit`, `fwd_c`) and a 40-digit fixture of
+their own in the last section (test_gpu_lie_forward.py).
 
 Every measure is ONE NUMBER PER RECORD.  Error of a result K against a truth T: max|K - T| / max|T|; the unit is
 D eps (1 + ||X||_1), the project's own (profiles/expm_accuracy.md).  A kernel is held to C units with
@@ -41,7 +45,7 @@ def cname(cls):
 
 # ------------------------------------------------------------------------------------------ inputs
 def _seed(cls, D, salt):
-    kinds = {'gen': 1, 'skew': 2, 'nilp': 3}
+    kinds = {'gen': 1, 'skew': 2, 'nilp': 3, 'shift': 4, 'tri': 5, 'edge': 6}
     return torch.Generator().manual_seed(int(kinds[cls[0]] * 1000003 + round(cls[1] * 1000) * 101 + D * 7 + salt * 13))
 
 
@@ -191,18 +195,49 @@ def frechet_degree(m, depth, max_order):
     return torch.where(m + depth <= max_order, m + depth, m.clamp(min=min(max_order, 2 ** 31 - 1)))
 
 
-def frechet_model(X, A, B, dtype, max_order=10000, tol=1e-32, plan=None):
+def expm_model(X, dtype, max_order=10000, tol=1e-32, plan=None):
+    """The forward part of `frechet_model`: E alone, Y = X / 2^s, Horner  P <- I + Y P / k  for k = m .. 1 with m from
+    `lie_plan(..., depth=0)`, then s squarings.  Returns (E, (s, m)); `plan` = (s, m) pins both per record.  Order 1
+    is the kernel's closed form exp(x), with the plan (0, 0)."""
+    X = X.to(dtype)
+    D = X.shape[-1]
+    batch = X.shape[:-2]
+    if D == 1:
+        z = torch.zeros(batch, dtype=torch.int64)
+        return torch.where(torch.isfinite(X), torch.exp(X), torch.full_like(X, float('nan'))), (z, z)
+    x = X.reshape(-1, D, D)
+    n = x.shape[0]
+    if plan is None:
+        s, m = lie_plan(x, max_order, tol, 0)[:2]
+    else:
+        s, m = (torch.as_tensor(t).expand(batch).reshape(-1) for t in plan[:2])
+    finite = torch.isfinite(x).all(-1).all(-1)
+    f = torch.ldexp(torch.ones(n, dtype=dtype), -s.to(torch.int32))[:, None, None]
+    y = torch.where(finite[:, None, None], x * f, torch.full_like(x, float('nan')))
+    eye = torch.eye(D, dtype=dtype).expand(n, D, D)
+    e = eye.clone()
+    for k in range(int(m.max()) if n else 0, 0, -1):
+        rk = torch.tensor(1.0, dtype=dtype) / torch.tensor(float(k), dtype=dtype)
+        e = torch.where((m >= k)[:, None, None], eye + (y @ e) * rk, e)
+    for q in range(int(s.max()) if n else 0):
+        e = torch.where((s > q)[:, None, None], e @ e, e)
+    return e.reshape(X.shape), (s.reshape(batch), m.reshape(batch))
+
+
+def frechet_model(X, A, B, dtype, max_order=10000, tol=1e-32, plan=None, with_e=False):
     """The kernel's formulas in `dtype`, batched over equal batch shapes: Y = X / 2^s, A' = A / 2^s, B' = B / 2^s,
     Horner  H <- (A' P^B + B' P^A + Y H) / k,  P^B <- (B' P + Y P^B) / k,  P^A <- (A' P + Y P^A) / k,
     P <- I + Y P / k  for k = m .. 1, then s times  H <- H E + L^A L^B + L^B L^A + E H,  L <- L E + E L,  E <- E E.
     `plan` = (s, m) pins the squarings and the degree (per record); otherwise they come from `lie_plan` in `dtype`.
-    Order 1 is the kernel's closed form exp(x) a (b)."""
+    Order 1 is the kernel's closed form exp(x) a (b).  `with_e` returns (derivative, E): the exponential the same
+    recurrences carry (a non-finite direction makes it NaN too, as in the kernel)."""
     X, A = X.to(dtype), A.to(dtype)
     B = None if B is None else B.to(dtype)
     D = X.shape[-1]
     if D == 1:
         ex = torch.where(torch.isfinite(X), torch.exp(X), torch.full_like(X, float('nan')))
-        return ex * A if B is None else ex * A * B
+        out = ex * A if B is None else ex * A * B
+        return (out, ex.expand_as(out)) if with_e else out
     shape = torch.broadcast_shapes(X.shape, A.shape, *(() if B is None else (B.shape,)))
     x = X.expand(shape).reshape(-1, D, D)
     a = A.expand(shape).reshape(-1, D, D)
@@ -238,7 +273,8 @@ def frechet_model(X, A, B, dtype, max_order=10000, tol=1e-32, plan=None):
             lb = torch.where(on, lb @ e + e @ lb, lb)
         la = torch.where(on, la @ e + e @ la, la)
         e = torch.where(on, e @ e, e)
-    return (la if b is None else h).reshape(shape)
+    out = (la if b is None else h).reshape(shape)
+    return (out, e.reshape(shape)) if with_e else out
 
 
 # ------------------------------------------------------------------------------------------ measures and verdicts
@@ -314,13 +350,16 @@ def class_verdicts(K, T, R, X, dtype, where, label, factor=1.0, show=False):
 def truncated_verdict(K, X, A, B, dtype, max_order, tol, margin=1e-3):
     """error / unit per record of a result computed with `max_order` / `tol` against the model in float64, with the
     squarings and the degree pinned to what `dtype` arithmetic gives.  A record whose term bound is within `margin`
-    of the limit may have taken the neighbouring degree: it gets the smaller of the two errors."""
-    depth = 1 if B is None else 2
+    of the limit may have taken the neighbouring degree: it gets the smaller of the two errors.  A None: the
+    exponential itself (`expm_model`, depth 0)."""
+    depth = 0 if A is None else (1 if B is None else 2)
     X = X.cpu().to(dtype)
     s, m, r_m, r_prev = lie_plan(X, max_order, tol)
 
     def at(mm):
         plan = (s, frechet_degree(mm, depth, max_order))
+        if A is None:
+            return c_of(K, expm_model(X, torch.float64, plan=plan)[0], X, dtype)
         return c_of(K, frechet_model(X, A.cpu(), None if B is None else B.cpu(), torch.float64, plan=plan), X, dtype)
 
     c = at(m)
@@ -362,3 +401,185 @@ def fixture_c_ref(D, depth):
     x, a, b, L, L2 = fixture_records(D)
     c = c_of(frechet_truth64(x, a, b if depth == 2 else None), L2 if depth == 2 else L, x, torch.float64)
     return {cls: float(c[sl].max()) for cls, sl in fixture_classes()}
+
+
+# ------------------------------------------------------------------------------------------ the forward kernels
+# Input classes, a conditioning unit and per-record verdicts for `ExpmOp` itself (test_gpu_lie_forward.py and
+# test_lie_host.py).  The unit of the Frechet tests above, D eps (1 + ||X||_1), is not a conditioning bound: on general
+# matrices of ||X||_1 = 80 a float32 transcription of the kernel's formulas is 4 of those units off and matrix_exp 100.
+# The forward kernels are held to the Frobenius error ||K - T||_F / ||T||_F in units of D eps max(1, cond_exp(X)),
+# cond_exp(X) = ||K(X)||_2 ||X||_F / ||e^X||_F, K(X) the D^2 x D^2 matrix of the Frechet derivative: the relative
+# change of e^X that a relative perturbation eps of X can cause, which no algorithm can be asked to beat.
+FWD_CLASSES = tuple(('gen', v) for v in (1e-3, 0.5, 8.0, 30.0, 60.0, 80.0)) + \
+    (('skew', 200.0), ('skew', 1000.0), ('nilp', 5.0)) + \
+    tuple(('shift', v) for v in (10.0, 40.0, 80.0)) + (('tri', 30.0), ('tri', 100.0)) + \
+    tuple(('edge', v) for v in (1.0, 2.0, 4.0, 8.0))
+FWD_CLASSES_F64 = FWD_CLASSES + (('shift', 300.0), ('gen', 300.0))     # float64 only: out of float32's range
+FWD_FIXTURE_ORDERS = (2, 3, 4, 5, 6, 7)
+FWD_FIXTURE_COUNT = 6                        # records per class and order in golden/lie_forward.npz
+FWD_N = 768                                  # the interleaved batch of the GPU tests: 12 wavefronts (cond_exp of it
+#                                              takes 0.5 s on the host at order 8)
+FWD_N_CLASS = 2000                           # records per class of the host's larger draw at orders <= 3
+SHIFT_NORM = 2.0                             # ||G||_1 of the shift classes, X = G - a I
+EDGE_BITS = 12                               # the edge classes' entries are multiples of ||X||_1 / 2^12
+
+
+# classes that miss the range condition (`in_range`) at an order, by their construction: e^X = e^-80 e^G, and max|e^G|
+# with ||G||_1 = 2 is as low as e^-2 at order 1 and below 0.66 on 49%, 11% and 1.7% of 2000 records at orders 1, 2, 3,
+# which puts max|e^X| under 2^10 tiny = 1.2e-35 in float32 (from order 4 on none of 2000 is; shift-40 covers 1..3)
+FWD_UNUSABLE = {('f32', D): (('shift', 80.0),) for D in (1, 2, 3)}
+
+
+def fwd_classes(dn, D):
+    """the classes of a dtype that are usable at an order, in the order the interleaved batches cycle through"""
+    out = FWD_CLASSES_F64 if dn == 'f64' else FWD_CLASSES
+    return tuple(c for c in out if c not in FWD_UNUSABLE.get((dn, D), ()))
+
+
+def build_fwd(cls, n, D, gen):
+    """n float64 matrices of a forward class.  gen, skew, nilp: `build_x`.  shift-a: G - a I with ||G||_1 = 2, the
+    exponential is e^-a e^G and every Horner step cancels.  tri-v: strictly upper part of 1-norm v, diagonal uniform
+    in [-3, 0]: non-normal.  edge-p: ||X||_1 = p, a power of two, exactly -- entries cut to multiples of p / 2^12
+    (every column sum is then exact in float32, in any order), the largest entry of the heaviest column raised by
+    what the cut took."""
+    kind, v = cls
+    if kind in ('gen', 'skew', 'nilp'):
+        return build_x(cls, n, D, gen)
+    if kind == 'shift':
+        return build_x(('gen', SHIFT_NORM), n, D, gen) - v * torch.eye(D, dtype=torch.float64)
+    if kind == 'tri':
+        up = build_x(('nilp', v), n, D, gen)
+        return up + torch.diag_embed(-3.0 * torch.rand(n, D, dtype=torch.float64, generator=gen))
+    assert kind == 'edge'
+    q = v / 2.0 ** EDGE_BITS
+    g = build_x(('gen', v), n, D, gen)
+    g = torch.sign(g) * torch.floor(g.abs() / q) * q
+    col = g.abs().sum(-2)
+    j = col.argmax(-1)
+    i = g.abs()[torch.arange(n), :, j].argmax(-1)
+    sgn = torch.where(g[torch.arange(n), i, j] < 0, -1.0, 1.0)
+    g[torch.arange(n), i, j] += sgn * (v - col[torch.arange(n), j])
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_inputs(cls, n, D, dn, salt=0):
+    """n records of a forward class, rounded to the dtype `dn`; shared, not to be written to"""
+    return build_fwd(cls, n, D, _seed(cls, D, salt + 100)).to(DT[dn])
+
+
+def fwd_class_index(n, dn, D):
+    """the class of record i of an interleaved batch: i mod the number of classes, so that every wavefront holds
+    every class, and with them every (s, m) from (0, 5) to (10, 22)"""
+    return torch.arange(n) % len(fwd_classes(dn, D))
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_batch(n, D, dn, salt=0):
+    """(X, class index) of the interleaved batch of n records: record i is record i // C of class i mod C"""
+    classes = fwd_classes(dn, D)
+    C = len(classes)
+    per = -(-n // C)
+    X = torch.stack([fwd_inputs(cls, per, D, dn, salt) for cls in classes], 1).reshape(per * C, D, D)[:n]
+    return X.contiguous(), fwd_class_index(n, dn, D)
+
+
+def in_range(T, dtype):
+    """the range condition of a usable record: 2^10 tiny <= max|e^X| <= 2^-10 max of the dtype: the entries that carry
+    the Frobenius error are normal numbers with ten bits of room, so the relative bound means what it says"""
+    fi = torch.finfo(dtype)
+    big = T.double().abs().amax((-2, -1))
+    return (big >= 2.0 ** 10 * fi.tiny) & (big <= 2.0 ** -10 * fi.max)
+
+
+def cond_exp(X):
+    """(cond_exp, ||e^X||_F) per record in float64: K(X) column by column from the block identity
+    expm([[X, E_ij], [0, X]])[:D, D:] over the D^2 unit directions, in chunks of records; order 1: |x|"""
+    X = X.double()
+    D = X.shape[-1]
+    x = X.reshape(-1, D, D)
+    if D == 1:
+        return x.abs().reshape(X.shape[:-2]), torch.exp(x).abs().reshape(X.shape[:-2])
+    n = x.shape[0]
+    dirs = torch.eye(D * D, dtype=torch.float64).reshape(D * D, D, D)
+    cond, nrm = torch.empty(n, dtype=torch.float64), torch.empty(n, dtype=torch.float64)
+    step = max(1, 2 ** 21 // (4 * D ** 4))
+    for at in range(0, n, step):
+        xc = x[at:at + step]
+        Z, (r, c) = _blocks(xc[:, None], dirs, None, torch.float64)
+        Z = torch.linalg.matrix_exp(Z)
+        K = Z[..., r, c].reshape(-1, D * D, D * D)                # row (i, j): vec L(X, E_ij) -- K transposed
+        ef = torch.linalg.matrix_norm(Z[:, 0, :D, :D])
+        cond[at:at + step] = torch.linalg.matrix_norm(K, 2) * torch.linalg.matrix_norm(xc) / ef
+        nrm[at:at + step] = ef
+    return cond.reshape(X.shape[:-2]), nrm.reshape(X.shape[:-2])
+
+
+def fwd_unit(X, dtype, cond=None):
+    """D eps max(1, cond_exp(X)) per record (`cond`: a cached cond_exp of the same records)"""
+    cond = cond_exp(X.cpu())[0] if cond is None else cond
+    return X.shape[-1] * torch.finfo(dtype).eps * cond.clamp(min=1.0)
+
+
+def fwd_err(K, T):
+    """||K - T||_F / ||T||_F per record; a non-finite result counts as inf"""
+    K, T = K.detach().cpu().double(), T.detach().cpu().double()
+    e = torch.linalg.matrix_norm(K - T) / torch.linalg.matrix_norm(T)
+    return torch.where(torch.isfinite(e), e, torch.full_like(e, float('inf')))
+
+
+def fwd_c(K, T, X, dtype, cond=None):
+    """error / unit per record"""
+    return fwd_err(K, T) / fwd_unit(X, dtype, cond)
+
+
+def fwd_truth64(X):
+    """matrix_exp in float64 on the inputs as they are (rounded to float32): the truth of float32 results, held to
+    the 40-digit fixture by test_lie_host.py; order 1: exp"""
+    X = X.cpu().double()
+    return torch.exp(X) if X.shape[-1] == 1 else torch.linalg.matrix_exp(X)
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_case(D, dn, salt=0):
+    """(X, class index, truth, cond_exp) of the interleaved batch the GPU tests judge at an order: float32 the
+    FWD_N-record draw with the float64 matrix_exp as truth, float64 the 40-digit fixture (orders 2..7; order 1: the
+    draw, exp in float64 is correctly rounded to an ulp).  The range condition is asserted on every record."""
+    if dn == 'f64' and D > 1:
+        X, T = fwd_fixture_records(D)
+        idx = fwd_class_index(X.shape[0], dn, D)
+    else:
+        X, idx = fwd_batch(FWD_N, D, dn, salt)
+        T = fwd_truth64(X)
+    ok = in_range(T, DT[dn])
+    assert bool(ok.all()), f'{dn} D={D}: records {torch.nonzero(~ok).reshape(-1)[:8].tolist()} out of range'
+    return X, idx, T, cond_exp(X)[0]
+
+
+def fwd_worst(c, idx, classes):
+    """{class name: worst value} of a per-record measure of an interleaved batch"""
+    return {cname(cls): float(c[idx == q].max()) for q, cls in enumerate(classes) if bool((idx == q).any())}
+
+
+def fwd_verdicts(c, idx, classes, cmax, label):
+    """every class of an interleaved batch held to cmax units; all failing classes are reported together"""
+    msgs = []
+    for q, cls in enumerate(classes):
+        rec = torch.nonzero(idx == q).reshape(-1)
+        bad = rec[~(c[rec] <= cmax)]
+        if bad.numel():
+            w = int(bad[torch.argmax(c[bad])])
+            msgs.append(f'{label} {cname(cls)}: {bad.numel()} of {rec.numel()} records over {cmax:.2f} units; worst '
+                        f'record {w} at {float(c[w]):.2f} units; first records {bad[:8].tolist()}')
+    assert not msgs, '\n'.join(msgs)
+
+
+@functools.lru_cache(maxsize=None)
+def fwd_fixture():
+    return np.load(os.path.join(GOLDEN, 'lie_forward.npz'))
+
+
+def fwd_fixture_records(D):
+    """(X, e^X at 40 digits) of an order of the forward fixture, float64, interleaved by class"""
+    g = fwd_fixture()
+    return torch.from_numpy(g[f'x_{D}']), torch.from_numpy(g[f't_{D}'])

@@ -243,3 +243,140 @@ def test_frechet_model_closed_forms_and_truncation(dn, D):
                 c = R.truncated_verdict(k, xc, ac, bb, dtype, max_order, tol)
                 msg = R.verdict(c, R.C_FLOOR, f'model {dn} D={D} {cls} max_order={max_order} tol={tol:g}')
                 assert msg is None, msg
+
+
+# ------------------------------------------------------------------------------------------ the forward kernels:
+# the classes, the conditioning unit and the model of tests/_lie_ref.py, before a GPU sees their bounds
+FWD_CASES = [('f32', D) for D in range(1, 9)] + [('f64', D) for D in range(1, 8)]
+
+
+def test_forward_fixture_is_the_interleaved_float64_draw():
+    import _lie_ref as R
+    g = R.fwd_fixture()
+    n = R.FWD_FIXTURE_COUNT * len(R.FWD_CLASSES_F64)
+    assert n == 120
+    for D in R.FWD_FIXTURE_ORDERS:
+        x, t = R.fwd_fixture_records(D)
+        assert x.shape == t.shape == (n, D, D) and x.dtype == t.dtype == torch.float64
+        assert torch.equal(x, R.fwd_batch(n, D, 'f64', salt=1)[0])
+        assert torch.isfinite(t).all()
+    assert g['over_x_4'].shape == g['over_log2_4'].shape == (6, 4, 4)
+    assert not ((g['over_log2_4'] > 1022) & (g['over_log2_4'] < 1026)).any() and (g['over_log2_4'].max((1, 2)) > 1026).all()
+
+
+@pytest.mark.parametrize('dn,D', FWD_CASES)
+def test_forward_class_invariants(dn, D):
+    """every record of every usable class is finite and inside the range condition (asserted by `fwd_case`); a class
+    left out at an order really misses it; the edge records have ||X||_1 a power of two bit for bit, where frexp
+    gives f = 0.5 and s = log2 + 1; the structured classes have their structure"""
+    import _lie_ref as R
+    dtype = R.DT[dn]
+    X, idx, T, cond = R.fwd_case(D, dn)
+    classes = R.fwd_classes(dn, D)
+    assert torch.isfinite(X).all() and torch.isfinite(T).all() and torch.isfinite(cond).all()
+    assert len(set(idx[:len(classes)].tolist())) == len(classes)            # every class in every run of records
+    for cls in R.FWD_UNUSABLE.get((dn, D), ()):
+        assert cls in (R.FWD_CLASSES_F64 if dn == 'f64' else R.FWD_CLASSES)
+        x = R.fwd_inputs(cls, R.FWD_N_CLASS, D, dn)
+        assert not bool(R.in_range(R.fwd_truth64(x), dtype).all()), cls
+    s, m = R.lie_plan(X)[:2]
+    if D > 1:
+        assert int(s.min()) == 0 and int(s.max()) == 10 and int(m.min()) == 5 and int(m.max()) >= 18
+    for q, cls in enumerate(classes):
+        x = X[idx == q]
+        if cls[0] == 'edge':
+            col = torch.zeros(x.shape[0], D, dtype=dtype)
+            for i in range(D):
+                col = col + x[:, i, :].abs()
+            assert torch.equal(col.amax(-1), torch.full((x.shape[0],), cls[1], dtype=dtype)), cls
+            assert torch.equal(R.norm1(x), torch.full((x.shape[0],), cls[1], dtype=torch.float64)), cls
+            if D > 1:
+                assert bool((s[idx == q] == int(np.log2(cls[1])) + 1).all()), cls
+        elif cls[0] == 'skew':
+            assert torch.equal(x, -x.mT)
+        elif cls[0] == 'nilp':
+            assert not bool(torch.tril(x).any())
+        elif cls[0] == 'tri':
+            assert not bool(torch.tril(x, -1).any())
+            d = torch.diagonal(x, dim1=-2, dim2=-1)
+            assert bool(((d <= 0) & (d >= -3)).all())
+        elif cls[0] == 'shift' and D > 1:
+            g = x.double() + cls[1] * torch.eye(D, dtype=torch.float64)
+            assert bool((R.norm1(g) <= R.SHIFT_NORM * (1 + 1e-5)).all())
+        elif cls[0] == 'gen' and D > 1:
+            assert torch.allclose(R.norm1(x), torch.tensor(cls[1], dtype=torch.float64), rtol=1e-6)
+
+
+def test_cond_exp_on_closed_forms():
+    """cond_exp of a normal matrix is ||X||_F ||e^X||_2 / ||e^X||_F: D^-1/2 ||X||_F for a skew-symmetric one,
+    |c| for c I; order 1: |x|"""
+    import _lie_ref as R
+    x = R.fwd_inputs(('skew', 200.0), 20, 4, 'f64')
+    c, nrm = R.cond_exp(x)
+    assert torch.allclose(c, torch.linalg.matrix_norm(x) / 2.0, rtol=1e-9)
+    assert torch.allclose(nrm, torch.full_like(nrm, 2.0), rtol=1e-12)
+    ci = -7.5 * torch.eye(3, dtype=torch.float64)[None]
+    assert torch.allclose(R.cond_exp(ci)[0], torch.tensor([7.5], dtype=torch.float64), rtol=1e-12)
+    assert torch.equal(R.cond_exp(torch.tensor([[[-3.0]], [[80.0]]]))[0], torch.tensor([3.0, 80.0], dtype=torch.float64))
+    assert torch.equal(R.fwd_unit(ci, torch.float32), 3 * 2.0 ** -23 * R.cond_exp(ci)[0])
+    assert torch.equal(R.fwd_unit(ci * 0, torch.float32), torch.tensor([3 * 2.0 ** -23], dtype=torch.float64))
+
+
+@pytest.mark.parametrize('D', range(2, 8))            # _lie_ref.FWD_FIXTURE_ORDERS
+def test_matrix_exp_float64_is_a_good_float32_truth(D):
+    """licenses matrix_exp in float64 as the truth of float32 results: on every fixture record its error against the
+    40-digit value is within 2^-10 eps(float32) / eps(float64) of the float64 unit, that is 2^-10 of the float32 one"""
+    import _lie_ref as R
+    assert D in R.FWD_FIXTURE_ORDERS
+    x, idx, t, cond = R.fwd_case(D, 'f64')
+    c = R.fwd_c(R.fwd_truth64(x), t, x, torch.float64, cond)
+    cmax = 2.0 ** -10 * torch.finfo(torch.float32).eps / torch.finfo(torch.float64).eps
+    R.fwd_verdicts(c, idx, R.fwd_classes('f64', D), cmax, f'matrix_exp float64 D={D}')
+
+
+@pytest.mark.parametrize('dn,D', [c for c in FWD_CASES if c[1] > 1])
+def test_expm_model_meets_half_the_forward_bound(dn, D):
+    """the bar of test_gpu_lie_forward.py is attainable: the kernel's formulas in the dtype stay within C_EXPM / 2
+    units of D eps max(1, cond_exp) on the records the GPU test judges (float32 against matrix_exp in float64, float64
+    against the 40-digit fixture); the factor 2 is the room a kernel gets for its different fma order"""
+    import _lie_ref as R
+    from test_gpu_lie import C_EXPM
+    x, idx, t, cond = R.fwd_case(D, dn)
+    c = R.fwd_c(R.expm_model(x, R.DT[dn])[0], t, x, R.DT[dn], cond)
+    R.fwd_verdicts(c, idx, R.fwd_classes(dn, D), C_EXPM / 2, f'model {dn} D={D}')
+
+
+@pytest.mark.parametrize('D', [2, 3])
+def test_expm_model_meets_half_the_forward_bound_on_2000_records(D):
+    """the same at 2000 records of every class, where the host can afford them (orders 2, 3: 36000 records, a
+    second); every one of them inside the range condition"""
+    import _lie_ref as R
+    from test_gpu_lie import C_EXPM
+    classes = R.fwd_classes('f32', D)
+    x = torch.cat([R.fwd_inputs(cls, R.FWD_N_CLASS, D, 'f32') for cls in classes])
+    idx = torch.arange(len(classes)).repeat_interleave(R.FWD_N_CLASS)
+    t = R.fwd_truth64(x)
+    assert bool(R.in_range(t, torch.float32).all())
+    c = R.fwd_c(R.expm_model(x, torch.float32)[0], t, x, torch.float32)
+    R.fwd_verdicts(c, idx, classes, C_EXPM / 2, f'model f32 D={D}, 2000 records')
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+@pytest.mark.parametrize('D', [2, 4])
+def test_expm_model_is_the_e_of_frechet_model(dn, D):
+    """one transcription: with (s, m) pinned, `expm_model` has the bits of the exponential that `frechet_model`
+    carries through the same recurrences, at full and at truncated degrees"""
+    import _lie_ref as R
+    dtype = R.DT[dn]
+    for cls in (('gen', 0.5), ('gen', 30.0), ('nilp', 5.0)):
+        x, a, b = R.inputs(cls, 64, D, dn)
+        for max_order, tol in ((10000, 1e-32), (1, 1e-32), (5, 1e-32), (10000, 1e-4), (10000, 0.0)):
+            e, plan = R.expm_model(x, dtype, max_order, tol)
+            s, m = R.lie_plan(x, max_order, tol)[:2]
+            assert torch.equal(plan[0], s) and torch.equal(plan[1], m)
+            assert int(m.max()) <= max_order
+            for bb in (None, b):
+                assert torch.equal(R.frechet_model(x, a, bb, dtype, plan=plan, with_e=True)[1], e)
+            assert torch.equal(R.expm_model(x, dtype, plan=plan)[0], e)
+        assert torch.equal(R.truncated_verdict(R.expm_model(x, torch.float64, plan=R.lie_plan(x, 5, 1e-32)[:2])[0],
+                                               x, None, None, dtype, 5, 1e-32), torch.zeros(64, dtype=torch.float64))
