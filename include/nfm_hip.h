@@ -217,6 +217,43 @@ int nfm_sym_pencil_dist_backward(int dtype, int M, int mode, int64_t n_outer, in
 /* largest M with a kernel for op = NFM_PENCIL_OP_*; 0 for an unknown dtype or op */
 int nfm_sym_pencil_max_order(int dtype, int op);
 
+/* EXTENSION (no counterpart in the reference): the sorted eigendecomposition mat = V diag(l) V^T of compact symmetric
+ * matrices, in the lane's registers (the arithmetic of nfm_sym_funm; its scale rule puts every finite record in range).
+ * flags = NFM_EIGH_ASCENDING, _DESCENDING or _ABS (ascending |l|, ties by l ascending), or'ed with NFM_EIGH_VECTORS.
+ * nfm_sym_eigh: without NFM_EIGH_VECTORS out holds records of the M values; with it, records of M + M M values:
+ * the values, then V row-major (column k belongs to value k).  The component of largest magnitude of every column is
+ * positive (the first such component among exact ties; the rule is applied after the sort).
+ * nfm_sym_eigh_backward: gmat = the gradient with respect to the compact record for the cotangents gval (M values)
+ * and gvec (M M values, row-major; NULL: the values alone, and NFM_EIGH_VECTORS in flags is ignored):
+ * S = V W V^T, W_kk = gval_k, W_kl = (B_kl - B_lk) / (2 (l_l - l_k)) with B = V^T gvec, returned as S_ii and 2 S_ij
+ * (the compact convention of nfm_sym_funm_backward).  The decomposition is recomputed from mat by the same code: the
+ * same order and signs.  THE GAP RULE: a pair with |l_k - l_l| <= 16 M eps max_i |l_i| has W_kl = 0, so the gradient
+ * of every finite record is finite.  `gmat` may be `gval`.
+ * A record with an entry that is not finite is NaN in every component (values, vectors, gradient); the other records
+ * do not notice.
+ * M in 1..nfm_sym_eigh_max_order(dtype, op), op = NFM_EIGH_OP_*.  Status precedence: that of nfm_sym_funm
+ * (NFM_EINVAL for unknown flags before NFM_ESIZE for M above the compiled cap, then the operands in argument
+ * order). */
+#define NFM_EIGH_ASCENDING 0
+#define NFM_EIGH_DESCENDING 1
+#define NFM_EIGH_ABS 2
+#define NFM_EIGH_VECTORS 4
+#define NFM_EIGH_OP_VALUES 0
+#define NFM_EIGH_OP_VECTORS 1
+#define NFM_EIGH_OP_VALUES_BACKWARD 2
+#define NFM_EIGH_OP_BACKWARD 3
+int nfm_sym_eigh(int dtype, int M, int flags, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
+                 const nfm_operand *out, void *stream);
+int nfm_sym_eigh_backward(int dtype, int M, int flags, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
+                          const nfm_operand *gval, const nfm_operand *gvec, const nfm_operand *gmat, void *stream);
+/* largest M with a kernel for op = NFM_EIGH_OP_*; 0 for an unknown dtype or op */
+int nfm_sym_eigh_max_order(int dtype, int op);
+/* CPU: what the kernels do after the sweeps, in place on n host records of order N <= 8 (NFM_ESIZE beyond): lam
+ * (n N values) and vec (n N N values, row-major, or NULL) are sorted into `order` (NFM_EIGH_ASCENDING .. _ABS, no
+ * flag) and the sign rule is applied; w (n N N values, or NULL) receives the weights 1 / (l_l - l_k) at [k][l] under
+ * the gap rule (0 on the diagonal).  NFM_EDTYPE; NFM_EINVAL for n < 0, an unknown order or lam == NULL with n > 0. */
+int nfm_sym_eigh_host_finish(int dtype, int order, int N, int64_t n, void *lam, void *vec, void *w);
+
 /* -------------------------------------------------------------- batched ---- */
 
 #define NFM_FLAG_TS_PERTURB 1 /* add (max|A| - min|A|) * 1e-12 to det for N in {2,3}:

@@ -432,6 +432,33 @@ class SymFunmFn(torch.autograd.Function):
         return S._funm_backward(mat, g, code, p, vmin, dtype).to(mat.dtype), None, None, None, None
 
 
+class SymEighFn(torch.autograd.Function):
+    """Sorted eigendecomposition of compact symmetric matrices (sym.sym_eigvals / sym.sym_eigh).  Nothing but `mat` is
+    saved: the backward kernels recompute the decomposition with the same code (the same order and signs) and apply
+    the gap rule, so the gradient is finite for every finite record -- unlike EigSymFn's 1 / (d_j - d_i).  Either
+    cotangent may be absent (no zeros are materialised for it)."""
+
+    @staticmethod
+    def forward(ctx, mat, order, vectors, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            res = S._eigh_forward(mat, order, vectors, dtype, None)
+        ctx.save_for_backward(mat)
+        ctx.cfg = (order, (res[0] if vectors else res).dtype)
+        ctx.set_materialize_grads(False)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, glam, gvec=None):
+        from . import sym as S
+        (mat,) = ctx.saved_tensors
+        if glam is None and gvec is None:
+            return None, None, None, None
+        order, dtype = ctx.cfg
+        return S._eigh_backward(mat, glam, gvec, order, dtype).to(mat.dtype), None, None, None
+
+
 def _to_input(g, like):
     """a gradient of the broadcast batch shape -> the shape and dtype of the input it belongs to"""
     return g.sum_to_size(like.shape).to(like.dtype)

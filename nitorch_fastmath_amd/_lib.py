@@ -23,6 +23,10 @@ FUN = {'exp': 0, 'log': 1, 'sqrt': 2, 'rsqrt': 3, 'pow': 4, 'clamp': 5}
 # include/nfm_hip.h: NFM_PENCIL_OP_* (the `op` of nfm_sym_pencil_max_order) and NFM_PENCIL_* (the `mode` of nfm_sym_pencil_eig)
 PENCIL_OP_FUNM, PENCIL_OP_FUNM_BACKWARD, PENCIL_OP_EIG, PENCIL_OP_DIST_BACKWARD = range(4)
 PENCIL_EIG, PENCIL_DIST2, PENCIL_DIST = range(3)
+# include/nfm_hip.h: NFM_EIGH_* (the order and the flag of nfm_sym_eigh) and NFM_EIGH_OP_* (the `op` of nfm_sym_eigh_max_order)
+EIGH_ORDER = {'ascending': 0, 'descending': 1, 'abs': 2}
+EIGH_VECTORS = 4
+EIGH_OP_VALUES, EIGH_OP_VECTORS, EIGH_OP_VALUES_BACKWARD, EIGH_OP_BACKWARD = range(4)
 # include/nfm_hip.h: NFM_SIMPLEX_*
 SX_SOFTMAX, SX_LOG_SOFTMAX, SX_LOGSUMEXP, SX_LOGIT, SX_SOFTMAX_BWD, SX_LOGSUMEXP_BWD, SX_LOG_SOFTMAX_BWD = range(7)
 SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
@@ -83,6 +87,11 @@ SIGNATURES = {
     'nfm_sym_pencil_eig': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp],
     'nfm_sym_pencil_dist_backward': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'nfm_sym_pencil_max_order': [_i, _i],
+    # (plain pointers for the same reason as nfm_sym_funm above; tests/test_symeig_host.py makes the canonical bad calls)
+    'nfm_sym_eigh': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp],
+    'nfm_sym_eigh_backward': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_sym_eigh_max_order': [_i, _i],
+    'nfm_sym_eigh_host_finish': [_i, _i, _i, _i64, _vp, _vp, _vp],
     'nfm_batch_inv': [_i, _i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_det': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],

@@ -26,6 +26,8 @@ __all__ = [
     'sym_matmul_solve',      # extension: fused Gauss-Newton step (not in the reference)
     # extensions: spectral functions of compact symmetric matrices (not in the reference)
     'sym_funm', 'sym_expm', 'sym_logm', 'sym_sqrtm', 'sym_rsqrtm', 'sym_powm', 'sym_clampm',
+    # extensions: sorted eigendecomposition of compact symmetric matrices (not in the reference)
+    'sym_eigvals', 'sym_eigh',
     # extensions: spectral functions of two compact symmetric matrices (not in the reference)
     'sym_pencil_funm', 'sym_geodesic', 'sym_geomean', 'sym_logmap', 'sym_expmap', 'sym_geneigvals', 'sym_dist',
     'sym_karcher_mean',
@@ -568,6 +570,140 @@ def sym_powm(mat, p, min=None, dtype=None, out=None):
 def sym_clampm(mat, min, dtype=None, out=None):
     """EXTENSION: projection onto `{A >= min I}`: the eigenvalues clamped from below (`sym_funm(mat, 'clamp')`)."""
     return sym_funm(mat, 'clamp', min=min, dtype=dtype, out=out)
+
+
+# ---------------------------------------------------------------- sorted eigendecomposition (extension)
+def _eigh_cap(dtype, op):
+    """largest order with a kernel for `op`: the compiled table of the library (`nfm_sym_eigh_max_order`)"""
+    return max_order('nfm_sym_eigh_max_order', dtype, op)
+
+
+def _eigh_order(order):
+    if order not in _lib.EIGH_ORDER:
+        raise ValueError(f"order must be one of {sorted(_lib.EIGH_ORDER)}, got {order!r}")
+    return _lib.EIGH_ORDER[order]
+
+
+def _alloc_field(out, shape, dtype, device, like):
+    """`_alloc_out` for a result with the batch of `like` and another number of components: a channel-first
+    (component-major) `like` hands its dim order on, as `_alloc_out` does for a result of its own shape"""
+    if (out is None and tuple(like.shape) != tuple(shape) and tuple(like.shape[:-1]) == tuple(shape[:-1])
+            and like.dim() >= 2 and like.stride(-1) != 1 and like.numel() > 0 and 0 not in like.stride()
+            and torch.empty_like(like, device='meta').stride() == like.stride()):
+        perm = sorted(range(like.dim()), key=lambda d: (-like.stride(d), d))
+        inv = [perm.index(d) for d in range(like.dim())]
+        return torch.empty([shape[d] for d in perm], dtype=dtype, device=device).permute(inv), None
+    return _alloc_out(out, shape, dtype, device, like=like)
+
+
+def _eigh_forward(mat, order, vectors, dtype, out):
+    """values `(..., M)`, or with `vectors` the pair (values, vectors): two views of one packed `(..., M + M*M)`"""
+    dev, dtype, (mat,) = prepare(dtype, mat)
+    M = _nb_prm(mat.shape[-1])
+    if M > _eigh_cap(dtype, _lib.EIGH_OP_VECTORS if vectors else _lib.EIGH_OP_VALUES):
+        from . import _symeig          # no kernel at this order: torch.linalg.eigh on the device
+        res = _symeig.forward(mat, order, vectors)
+        return res if vectors else _deliver(res, out)
+    batch = mat.shape[:-1]
+    if vectors:
+        packed = torch.empty(tuple(batch) + (M + M * M,), dtype=dtype, device=dev)
+        b = Batch(batch, [mat, packed], [1, 1])
+        launch(_lib.lib().nfm_sym_eigh, dev, dtype, (M, order | _lib.EIGH_VECTORS), b)
+        return packed[..., :M], packed[..., M:].unflatten(-1, (M, M))
+    out, _ = _alloc_field(out, tuple(batch) + (M,), dtype, dev, mat)
+    b = Batch(batch, [mat, out], [1, 1])
+    launch(_lib.lib().nfm_sym_eigh, dev, dtype, (M, order), b)
+    return out
+
+
+def _eigh_backward(mat, glam, gvec, order, dtype):
+    """the compact gradient for the cotangents of the values and / or of the vectors (either may be None)"""
+    dev, dtype, (mat, glam, gvec) = prepare(dtype, mat, glam, gvec)
+    M = _nb_prm(mat.shape[-1])
+    if M > _eigh_cap(dtype, _lib.EIGH_OP_VALUES_BACKWARD if gvec is None else _lib.EIGH_OP_BACKWARD):
+        from . import _symeig
+        if M > _eigh_cap(dtype, _lib.EIGH_OP_VECTORS):
+            return _symeig.backward(mat, glam, gvec, order)
+        # the split route: the forward kernel recomputes the decomposition (its order and its signs, which another
+        # solver does not reproduce where a sign is decided by a tie) and torch applies the formula
+        lam, V = _eigh_forward(mat, order, True, dtype, None)
+        return _symeig.backward_from(lam, V, ~torch.isfinite(mat).all(-1), glam, gvec)
+    batch = mat.shape[:-1]
+    gmat, _ = _alloc_out(None, tuple(mat.shape), dtype, dev, like=mat)
+    if glam is None:               # a stride-0 record of zeros
+        glam = torch.zeros(M, dtype=dtype, device=dev)
+    glam = expand_batch(batch, glam, 1)
+    if gvec is None:
+        b = Batch(batch, [mat, glam, gmat], [1, 1, 1])
+        launch(_lib.lib().nfm_sym_eigh_backward, dev, dtype, (M, order), b, slots=(0, 1, None, 2))
+    else:
+        # one row-major record of M * M values (a view unless the two matrix dims cannot be merged)
+        gvec = expand_batch(batch, gvec, 2).reshape(tuple(batch) + (M * M,))
+        b = Batch(batch, [mat, glam, gvec, gmat], [1, 1, 1, 1])
+        launch(_lib.lib().nfm_sym_eigh_backward, dev, dtype, (M, order | _lib.EIGH_VECTORS), b)
+    return gmat
+
+
+def sym_eigvals(mat, order='ascending', dtype=None, out=None):
+    r"""EXTENSION (not in the reference): the eigenvalues of compact symmetric matrices, sorted.
+
+    One read of the `K = M(M+1)/2` values and one write of `M`, the decomposition in the registers of one lane (the
+    fast arithmetic of `qr.eig_sym`, which scales: every finite matrix is in range), instead of
+    `sym_to_full` -> `eig_sym` -> a sort in torch.
+
+    Parameters
+    ----------
+    mat : `(..., M*(M+1)//2) tensor`
+    order : {'ascending', 'descending', 'abs'}
+        'ascending' is the order of `torch.linalg.eigh`; 'abs' sorts ascending by `|l|`, ties by the value ascending
+        (`|l1| <= |l2| <= |l3|`, the Frangi / Sato convention of Hessian filters).
+    dtype, out : as `sym_det`.  A channel-first field hands its layout on to the values and to the gradient.
+
+    Returns `(..., M)`.  A matrix with an entry that is not finite gives NaN in all its values and in its gradient;
+    its neighbours are untouched.  No exception, no host synchronisation: forward and backward can be captured in a
+    graph.
+
+    Differentiable once with respect to `mat` (only `mat` is saved; the backward pass recomputes the decomposition):
+    the gradient is `V diag(g) V^T` in the compact convention of the module, what autograd gives through
+    `sym_to_full`.  See `sym_eigh` for the gap rule of the eigenvectors' gradient.
+    Orders above the compiled caps (8) run `torch.linalg.eigh` on the device.
+    """
+    code = _eigh_order(order)
+    _nb_prm(torch.as_tensor(mat).shape[-1])
+    if needs_grad(mat):
+        _grad_guard(out)
+        from ._autograd import SymEighFn
+        return SymEighFn.apply(torch.as_tensor(mat), code, False, dtype)
+    return _eigh_forward(mat, code, False, dtype, out)
+
+
+def sym_eigh(mat, order='ascending', dtype=None):
+    r"""EXTENSION (not in the reference): eigenvalues `(..., M)` and eigenvectors `(..., M, M)` of compact symmetric
+    matrices, sorted as `sym_eigvals`; column `k` of the vectors belongs to value `k`.
+
+    Signs: the component of largest magnitude of each returned eigenvector is positive (the first such component
+    among exact ties); the rule is applied after the sort.  Bad records, range and graph capture as `sym_eigvals`
+    (NaN in the values, the vectors and the gradient).  The two results are views of one packed tensor.
+
+    Differentiable once with respect to `mat`; the backward pass recomputes the decomposition with the same code, so
+    with the same order and signs.  For the cotangents `gl` and `gV` (either may be absent): `B = V^T gV`,
+    `W_kk = gl_k`, `W_kl = (B_kl - B_lk) / (2 (l_l - l_k))`, `S = V W V^T`, returned as `S_ii` and `2 S_ij`.
+
+    THE GAP RULE: a pair of eigenvalues with `|l_k - l_l| <= 16 M eps max_i |l_i|` gets `W_kl = 0`.  `16 M eps` is the
+    bar the sweeps are held to; closer pairs are numerically one eigenspace.  The gradient is therefore finite for
+    every finite matrix, isotropic and repeated ones included, and exact for any loss that does not depend on the
+    choice of basis inside an eigenspace.
+
+    Orders above the compiled caps (8) run `torch.linalg.eigh` on the device with the same sort, sign rule and
+    gradient formula.  An order with a forward kernel and no backward kernel (8 for the float64 gradient with `gV`)
+    recomputes the decomposition with the forward kernel and applies the formula in torch.
+    """
+    code = _eigh_order(order)
+    _nb_prm(torch.as_tensor(mat).shape[-1])
+    if needs_grad(mat):
+        from ._autograd import SymEighFn
+        return SymEighFn.apply(torch.as_tensor(mat), code, True, dtype)
+    return _eigh_forward(mat, code, True, dtype, None)
 
 
 # ---------------------------------------------------------------- two-matrix spectral functions (extension)
