@@ -254,6 +254,57 @@ int nfm_sym_eigh_max_order(int dtype, int op);
  * the gap rule (0 on the diagonal).  NFM_EDTYPE; NFM_EINVAL for n < 0, an unknown order or lam == NULL with n > 0. */
 int nfm_sym_eigh_host_finish(int dtype, int order, int N, int64_t n, void *lam, void *vec, void *w);
 
+/* EXTENSION (no counterpart in the reference): Cholesky kernels of compact symmetric positive definite matrices,
+ * mat = L L^T with L lower triangular, in the lane's registers; every record is read once.  Compact in, compact out:
+ * L_ij (i >= j) is stored where the compact layout stores (i, j), so the first M values of a factor are its diagonal.
+ * nfm_sym_chol: op =
+ *   NFM_CHOL_FACTOR              out = L (M (M + 1) / 2 values); vec is not read (NULL)
+ *   NFM_CHOL_APPLY_L / _LT       out = L vec / L^T vec (M values)
+ *   NFM_CHOL_APPLY_LINV / _LTINV out = L^-1 vec / L^-T vec (M values); or'ed with NFM_CHOL_FACTORED, the four apply
+ *                                ops read `mat` as a factor that is already there (the result of NFM_CHOL_FACTOR)
+ *   NFM_CHOL_LOGDET              out = log det mat = 2 sum_i log L_ii (one value); vec is not read (NULL)
+ *   NFM_CHOL_MAHA / _MAHA_SQRT   out = vec^T mat^-1 vec = |L^-1 vec|^2 (one value) / its root
+ *   NFM_CHOL_LOGPDF              out = -(M log 2 pi + log det mat + vec^T mat^-1 vec) / 2 (one value)
+ * nfm_sym_chol_backward: op = NFM_CHOL_LOGDET, _MAHA, _MAHA_SQRT or _LOGPDF; gout = the cotangent of the value (one
+ * per record); gpacked = records of M (M + 1) / 2 + M values (NFM_CHOL_LOGDET: M (M + 1) / 2, vec is not read): the
+ * gradient with respect to mat in the compact convention of nfm_sym_funm_backward (S_ii, 2 S_ij), then the one with
+ * respect to vec.  With w = mat^-1 vec: LOGDET S = gout mat^-1; MAHA S = -gout w w^T, gvec = 2 gout w; MAHA_SQRT the
+ * same with gout / (2 d), zero where d == 0; LOGPDF S = -gout (mat^-1 - w w^T) / 2, gvec = -gout w.  The factor is
+ * recomputed from mat.
+ * A record with an entry of mat or vec that is not finite, or with a pivot a_jj - sum_k l_jk^2 that is not > 0, is NaN
+ * in every value (results and gradients); the other records do not notice.  Nothing is scaled and nothing overflows
+ * that mat and its root do not.
+ * M in 1..nfm_sym_chol_max_order(dtype, class), class = NFM_CHOL_CLASS_*.  Status precedence: that of nfm_sym_funm
+ * (NFM_EINVAL for an unknown op, or NFM_CHOL_FACTORED on an op that is not an apply, before NFM_ESIZE for M above the
+ * compiled cap, then the operands in argument order; an operand the op does not read is not looked at). */
+#define NFM_CHOL_FACTOR 0
+#define NFM_CHOL_APPLY_L 1
+#define NFM_CHOL_APPLY_LT 2
+#define NFM_CHOL_APPLY_LINV 3
+#define NFM_CHOL_APPLY_LTINV 4
+#define NFM_CHOL_LOGDET 5
+#define NFM_CHOL_MAHA 6
+#define NFM_CHOL_MAHA_SQRT 7
+#define NFM_CHOL_LOGPDF 8
+#define NFM_CHOL_FACTORED 16
+#define NFM_CHOL_CLASS_FACTOR 0
+#define NFM_CHOL_CLASS_APPLY 1
+#define NFM_CHOL_CLASS_SCALAR 2
+#define NFM_CHOL_CLASS_BACKWARD 3
+int nfm_sym_chol(int dtype, int M, int op, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
+                 const nfm_operand *vec, const nfm_operand *out, void *stream);
+int nfm_sym_chol_backward(int dtype, int M, int op, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
+                          const nfm_operand *vec, const nfm_operand *gout, const nfm_operand *gpacked, void *stream);
+/* largest M with a kernel for op_class = NFM_CHOL_CLASS_*; 0 for an unknown dtype or class */
+int nfm_sym_chol_max_order(int dtype, int op_class);
+/* CPU: the record routines the kernels run, on n contiguous host records of order M <= 8 (NFM_ESIZE beyond): mat (n
+ * M (M + 1) / 2 values), vec (n M values, or NULL for an op without one), out (n records of the op's result).  With
+ * gout (n values) given, the backward routine of `op` runs instead and out receives the packed gradients.
+ * NFM_EDTYPE; NFM_EINVAL for n < 0, an unknown op (with gout: an op without a gradient), or a null mat, out or needed
+ * vec with n > 0. */
+int nfm_sym_chol_host(int dtype, int M, int op, int64_t n, const void *mat, const void *vec, const void *gout,
+                      void *out);
+
 /* -------------------------------------------------------------- batched ---- */
 
 #define NFM_FLAG_TS_PERTURB 1 /* add (max|A| - min|A|) * 1e-12 to det for N in {2,3}:

@@ -459,6 +459,33 @@ class SymEighFn(torch.autograd.Function):
         return S._eigh_backward(mat, glam, gvec, order, dtype).to(mat.dtype), None, None, None
 
 
+class SymCholFn(torch.autograd.Function):
+    """The scalar Cholesky ops of compact symmetric matrices (sym.sym_logdet / sym_mahalanobis / sym_gauss_logpdf).
+    Nothing but the inputs is saved: one backward kernel recomputes the factor and writes the packed gradient
+    [K | M], returned as two views reduced to the inputs' own (possibly broadcast) shapes."""
+
+    @staticmethod
+    def forward(ctx, mat, vec, op, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            res = S._chol_forward(op, S._lib.CHOL_CLASS_SCALAR, mat, vec, dtype, None, None)
+        ctx.save_for_backward(mat, vec)
+        ctx.cfg = (op, res.dtype)
+        return res
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        from . import sym as S
+        mat, vec = ctx.saved_tensors
+        op, dtype = ctx.cfg
+        packed = S._chol_backward(op, mat, vec, g, dtype)
+        K = mat.shape[-1]
+        gmat = _to_input(packed[..., :K], mat) if ctx.needs_input_grad[0] else None
+        gvec = _to_input(packed[..., K:], vec) if vec is not None and ctx.needs_input_grad[1] else None
+        return gmat, gvec, None, None
+
+
 def _to_input(g, like):
     """a gradient of the broadcast batch shape -> the shape and dtype of the input it belongs to"""
     return g.sum_to_size(like.shape).to(like.dtype)

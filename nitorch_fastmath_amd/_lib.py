@@ -27,6 +27,12 @@ PENCIL_EIG, PENCIL_DIST2, PENCIL_DIST = range(3)
 EIGH_ORDER = {'ascending': 0, 'descending': 1, 'abs': 2}
 EIGH_VECTORS = 4
 EIGH_OP_VALUES, EIGH_OP_VECTORS, EIGH_OP_VALUES_BACKWARD, EIGH_OP_BACKWARD = range(4)
+# include/nfm_hip.h: NFM_CHOL_* (the `op` of nfm_sym_chol), NFM_CHOL_FACTORED (its flag) and NFM_CHOL_CLASS_* (the
+# `op_class` of nfm_sym_chol_max_order)
+CHOL_FACTOR, CHOL_LOGDET, CHOL_MAHA, CHOL_MAHA_SQRT, CHOL_LOGPDF = 0, 5, 6, 7, 8
+CHOL_APPLY = {'L': 1, 'LT': 2, 'Linv': 3, 'LTinv': 4}
+CHOL_FACTORED = 16
+CHOL_CLASS_FACTOR, CHOL_CLASS_APPLY, CHOL_CLASS_SCALAR, CHOL_CLASS_BACKWARD = range(4)
 # include/nfm_hip.h: NFM_SIMPLEX_*
 SX_SOFTMAX, SX_LOG_SOFTMAX, SX_LOGSUMEXP, SX_LOGIT, SX_SOFTMAX_BWD, SX_LOGSUMEXP_BWD, SX_LOG_SOFTMAX_BWD = range(7)
 SX_IMPLICIT_IN, SX_IMPLICIT_OUT, SX_MAX_K = 1, 2, 48
@@ -92,6 +98,11 @@ SIGNATURES = {
     'nfm_sym_eigh_backward': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'nfm_sym_eigh_max_order': [_i, _i],
     'nfm_sym_eigh_host_finish': [_i, _i, _i, _i64, _vp, _vp, _vp],
+    # (plain pointers for the same reason as nfm_sym_funm above; tests/test_symchol_host.py makes the canonical bad calls)
+    'nfm_sym_chol': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp],
+    'nfm_sym_chol_backward': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_sym_chol_max_order': [_i, _i],
+    'nfm_sym_chol_host': [_i, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_batch_inv': [_i, _i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_det': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],

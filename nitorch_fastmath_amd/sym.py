@@ -31,6 +31,8 @@ __all__ = [
     # extensions: spectral functions of two compact symmetric matrices (not in the reference)
     'sym_pencil_funm', 'sym_geodesic', 'sym_geomean', 'sym_logmap', 'sym_expmap', 'sym_geneigvals', 'sym_dist',
     'sym_karcher_mean',
+    # extensions: Cholesky kernels of compact symmetric positive definite matrices (not in the reference)
+    'sym_chol', 'sym_chol_apply', 'sym_logdet', 'sym_mahalanobis', 'sym_gauss_logpdf',
 ]
 import ctypes
 from math import sqrt
@@ -704,6 +706,162 @@ def sym_eigh(mat, order='ascending', dtype=None):
         from ._autograd import SymEighFn
         return SymEighFn.apply(torch.as_tensor(mat), code, True, dtype)
     return _eigh_forward(mat, code, True, dtype, None)
+
+
+# ---------------------------------------------------------------- Cholesky kernels (extension)
+def _chol_cap(dtype, cls):
+    """largest order with a kernel for the class: the compiled table of the library (`nfm_sym_chol_max_order`)"""
+    return max_order('nfm_sym_chol_max_order', dtype, cls)
+
+
+def _chol_shapes(mat, vec):
+    """(M, K) of the compact matrix, checked against the vector"""
+    K = torch.as_tensor(mat).shape[-1]
+    M = _nb_prm(K)
+    if vec is not None and torch.as_tensor(vec).shape[-1] != M:
+        raise ValueError(f'vec has {torch.as_tensor(vec).shape[-1]} components, a matrix of {K} compact values '
+                         f'is of order {M}')
+    return M, K
+
+
+def _chol_route(name, dtype, mat, vec=None, **kw):
+    """the torch composition (`_symchol.py`) on the device: orders without a kernel, and the differentiable factor"""
+    from . import _symchol
+    _, _, ts = prepare(dtype, mat, vec, grad_ok=True)
+    return getattr(_symchol, name)(*[t for t in ts if t is not None], **kw)
+
+
+_CHOL_ROUTE = {_lib.CHOL_FACTOR: ('chol', {}), _lib.CHOL_LOGDET: ('logdet', {}),
+               _lib.CHOL_MAHA: ('mahalanobis', {'squared': True}), _lib.CHOL_MAHA_SQRT: ('mahalanobis', {'squared': False}),
+               _lib.CHOL_LOGPDF: ('gauss_logpdf', {})}
+
+
+def _chol_forward(op, cls, mat, vec, dtype, out, route):
+    """one forward launch of `nfm_sym_chol`: the factor `(..., K)`, an applied vector `(..., M)` or a scalar `(...)`"""
+    dev, dtype, (mat, vec) = prepare(dtype, mat, vec)
+    M, K = _chol_shapes(mat, vec)
+    if M > _chol_cap(dtype, cls):                # no kernel at this order: the torch composition (_symchol.py)
+        name, kw = route
+        from . import _symchol
+        return _deliver(getattr(_symchol, name)(*([mat] if vec is None else [mat, vec]), **kw), out)
+    batch = mat.shape[:-1] if vec is None else broadcast_shapes(mat.shape[:-1], vec.shape[:-1])
+    if cls == _lib.CHOL_CLASS_FACTOR:
+        out, _ = _alloc_out(out, tuple(mat.shape), dtype, dev, like=mat)
+        nco = 1
+    elif cls == _lib.CHOL_CLASS_APPLY:
+        out, _ = _alloc_field(out, tuple(batch) + (M,), dtype, dev, vec)
+        nco = 1
+    else:
+        out, _ = _alloc_out(out, tuple(batch), dtype, dev)
+        nco = 0
+    if vec is None:
+        b = Batch(batch, [mat, out], [1, nco])
+        launch(_lib.lib().nfm_sym_chol, dev, dtype, (M, op), b, slots=(0, None, 1))
+    else:
+        b = Batch(batch, [expand_batch(batch, mat, 1), expand_batch(batch, vec, 1), out], [1, 1, nco])
+        launch(_lib.lib().nfm_sym_chol, dev, dtype, (M, op), b)
+    return out
+
+
+def _chol_backward(op, mat, vec, gout, dtype):
+    """the packed gradient `(..., K + M)` (`sym_logdet`: `(..., K)`) of a scalar op for the cotangent `gout`"""
+    dev, dtype, (mat, vec, gout) = prepare(dtype, mat, vec, gout)
+    M, K = _chol_shapes(mat, vec)
+    batch = tuple(gout.shape)
+    packed = torch.empty(batch + (K + (0 if vec is None else M),), dtype=dtype, device=dev)
+    gout = gout.contiguous()
+    if vec is None:
+        b = Batch(batch, [expand_batch(batch, mat, 1), gout, packed], [1, 0, 1])
+        launch(_lib.lib().nfm_sym_chol_backward, dev, dtype, (M, op), b, slots=(0, None, 1, 2))
+    else:
+        b = Batch(batch, [expand_batch(batch, mat, 1), expand_batch(batch, vec, 1), gout, packed], [1, 1, 0, 1])
+        launch(_lib.lib().nfm_sym_chol_backward, dev, dtype, (M, op), b)
+    return packed
+
+
+def _chol_scalar(op, mat, vec, dtype, out):
+    M, _ = _chol_shapes(mat, vec)
+    route = _CHOL_ROUTE[op]
+    if needs_grad(mat, vec):
+        _grad_guard(out)
+        _, cdt, _ = prepare(dtype, mat, vec, grad_ok=True)
+        if M > min(_chol_cap(cdt, _lib.CHOL_CLASS_SCALAR), _chol_cap(cdt, _lib.CHOL_CLASS_BACKWARD)):
+            return _chol_route(route[0], dtype, mat, vec, **route[1])     # torch differentiates the composition
+        from ._autograd import SymCholFn
+        return SymCholFn.apply(torch.as_tensor(mat), None if vec is None else torch.as_tensor(vec), op, dtype)
+    return _chol_forward(op, _lib.CHOL_CLASS_SCALAR, mat, vec, dtype, out, route)
+
+
+def sym_chol(mat, dtype=None, out=None):
+    r"""EXTENSION (not in the reference): the Cholesky factor of compact symmetric positive definite matrices.
+
+    Returns `(..., K)`, `K = M(M+1)/2`: the lower factor `L` with `A = L L^T`, `L_ij` (`i >= j`) stored where the
+    compact layout stores `(i, j)`, so `sym_diag` of the result is the diagonal of `L`.  One read of the `K` values and
+    one write, the factorisation in the registers of one lane.
+
+    BAD RECORDS (all the Cholesky functions): a matrix (or vector) with an entry that is not finite, or with a pivot
+    `d_j = a_jj - sum_k l_jk^2` that is not `> 0` (NaN, zero and negative included), gives NaN in every value of its
+    result and of its gradient; its neighbours are untouched.  No exception, no host synchronisation: a call can be
+    captured in a graph.  Nothing is scaled: `sym_chol(s^2 A) == s * sym_chol(A)` bit for bit for a power of two `s`.
+
+    dtype, out : as `sym_det`; `out=mat` (in place) is allowed.  With `requires_grad` the factor is computed by a torch
+    composition on the device (`torch.linalg.cholesky_ex`): there is no backward kernel for the factor itself.  Orders
+    above the compiled cap (8) take the same composition.
+    """
+    _chol_shapes(mat, None)
+    if needs_grad(mat):
+        _grad_guard(out)
+        return _chol_route('chol', dtype, mat)
+    return _chol_forward(_lib.CHOL_FACTOR, _lib.CHOL_CLASS_FACTOR, mat, None, dtype, out, _CHOL_ROUTE[_lib.CHOL_FACTOR])
+
+
+def sym_chol_apply(mat, vec, op, factored=False, dtype=None, out=None):
+    r"""EXTENSION: apply the Cholesky factor of compact SPD matrices `(..., K)` to vectors `(..., M)`.
+
+    op : 'L' for `L v` (colouring a white sample), 'LT' for `L^T v`, 'Linv' for `L^-1 v` (whitening), 'LTinv' for
+        `L^-T v`.
+    factored : `mat` already is the result of `sym_chol`, so one factorisation serves many vectors (same bits).
+    Either operand may be broadcast, as in `sym_matvec`.  Bad records, `dtype`, `out` and gradients as `sym_chol`.
+    """
+    if op not in _lib.CHOL_APPLY:
+        raise ValueError(f"op must be one of {sorted(_lib.CHOL_APPLY)}, got {op!r}")
+    _chol_shapes(mat, vec)
+    if needs_grad(mat, vec):
+        _grad_guard(out)
+        return _chol_route('chol_apply', dtype, mat, vec, op=op, factored=bool(factored))
+    code = _lib.CHOL_APPLY[op] | (_lib.CHOL_FACTORED if factored else 0)
+    return _chol_forward(code, _lib.CHOL_CLASS_APPLY, mat, vec, dtype, out,
+                         ('chol_apply', {'op': op, 'factored': bool(factored)}))
+
+
+def sym_logdet(mat, dtype=None, out=None):
+    r"""EXTENSION: `log det A = 2 sum_i log L_ii` of compact SPD matrices, `(...)`.  Finite wherever `A` and its root
+    are (the determinant itself overflows float32 at 8x8 with entries of 1e6); NaN, not `-inf`, for a singular record.
+
+    Differentiable once (one backward kernel, nothing but `mat` saved): `S = g A^-1`, returned as `S_ii`, `2 S_ij`.
+    Bad records, `dtype`, `out` and orders above the cap as `sym_chol`.
+    """
+    return _chol_scalar(_lib.CHOL_LOGDET, mat, None, dtype, out)
+
+
+def sym_mahalanobis(mat, vec, squared=True, dtype=None, out=None):
+    r"""EXTENSION: `v^T A^-1 v = |L^-1 v|^2` of compact SPD matrices and vectors, `(...)`, or its root with
+    `squared=False`.  One pass: `K + M` values read, one written.  Either operand may be broadcast.
+
+    Differentiable once in `mat` and `vec`: with `w = A^-1 v`, `S = -g w w^T` and `g_v = 2 g w`; for the root the same
+    with `g / (2 d)`, exactly zero where `d = 0` (finite at `v = 0`).  Bad records, `dtype`, `out` as `sym_chol`.
+    """
+    return _chol_scalar(_lib.CHOL_MAHA if squared else _lib.CHOL_MAHA_SQRT, mat, vec, dtype, out)
+
+
+def sym_gauss_logpdf(mat, resid, dtype=None, out=None):
+    r"""EXTENSION: the Gaussian log-density `-(M log 2 pi + log det A + r^T A^-1 r) / 2` of residuals `(..., M)` under
+    compact covariances `(..., K)`, `(...)`.  One pass: `K + M` values read, one written.
+
+    Differentiable once in `mat` and `resid`: `S = -g (A^-1 - w w^T) / 2`, `g_r = -g w`, `w = A^-1 r`.  Bad records,
+    `dtype`, `out` as `sym_chol`.
+    """
+    return _chol_scalar(_lib.CHOL_LOGPDF, mat, resid, dtype, out)
 
 
 # ---------------------------------------------------------------- two-matrix spectral functions (extension)
