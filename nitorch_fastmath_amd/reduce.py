@@ -126,8 +126,10 @@ def _dim_groups(input, dim):
     return groups if len(groups) > 1 else None
 
 
-# what a later stage does with the partial results of an earlier one
-_STAGE2 = {_lib.RED_NANSUM: _lib.RED_NANSUM, _lib.RED_SUM: _lib.RED_SUM, _lib.RED_NANCOUNT: _lib.RED_SUM,
+# what a later stage does with the partial results of an earlier one.  The partial sums of nansum are summed
+# plainly: the first stage has omitted the NaNs of the data, and a partial sum that is NaN all the same (+inf and
+# -inf among its values) must reach the result, not be omitted in its turn.
+_STAGE2 = {_lib.RED_NANSUM: _lib.RED_SUM, _lib.RED_SUM: _lib.RED_SUM, _lib.RED_NANCOUNT: _lib.RED_SUM,
            _lib.RED_NANSUMSQ: _lib.RED_SUM, _lib.RED_NANMAX: _lib.RED_NANMAX, _lib.RED_NANMIN: _lib.RED_NANMIN,
            _lib.RED_MAX: _lib.RED_MAX, _lib.RED_MIN: _lib.RED_MIN}
 

@@ -744,3 +744,129 @@ def test_moments_of_offset_data(dev, dn, offset, variant):
     print(f'MOMENTS {dn} offset={offset:g} {variant}: {judged} slices judged; worst error/bound ' +
           ' '.join(f'{k}={v:.3g}' for k, v in sorted(ratios.items())))
     assert judged > 10_000 and max(ratios.values()) <= 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Sums, extrema and indices on the same routes, on the hard slices of tests/_reduce_ref.py (wide exponent ranges,
+# cancellation, values at the top of the format, ties across lanes and chunks, a single late NaN, signed zeros,
+# subnormals, infinities): per-slice verdicts against the fsum truth and the derived sum bound.
+#
+# adjacent middle dims, reduced in place as (5, 420, 33): FLAT, COMB_LDS with A = 33 lanes, 6 / 13 chunks
+# (lane-per-output fold), and ind2sub over two reduced dims
+MID_SHAPE, MID_DIMS = (5, 70, 6, 33), (1, 2)
+
+
+def _hard_inputs(dn, dev):
+    """(route, numpy array, kinds of its slices, dim, device tensors, judge indices?) of every input; the truth is
+    shared by the tensors of an array (the same values at other alignments)"""
+    import _reduce_ref as RR
+    seed = 0
+    for shape, dim in MOMENT_ROUTES:
+        seed += 1
+        for x, kinds in RR.make_hard_batches(shape, dim, dn, 100 * seed):
+            flat = np.concatenate([np.zeros(1, x.dtype), x.reshape(-1)])
+            yield f'{shape} dim={dim}', x, kinds, dim, (t(x, dev), t(flat, dev)[1:].reshape(shape)), True
+    for dim in STAGED_DIMS:          # values: the staged path; indices: the permuting copy
+        seed += 1
+        for x, kinds in RR.make_hard_batches(STAGED_SHAPE, dim, dn, 100 * seed):
+            yield f'staged {dim}', x, kinds, dim, (t(x, dev),), True
+    inv = list(np.argsort(PERM))
+    view_shape = tuple(PERM_BASE[p] for p in PERM)
+    for dim in PERM_DIMS:
+        seed += 1
+        for x, kinds in RR.make_hard_batches(view_shape, dim, dn, 100 * seed):
+            xd = t(x.transpose(inv), dev).permute(PERM)
+            assert not xd.is_contiguous() and tuple(xd.shape) == view_shape
+            yield f'permuted view {dim}', x, kinds, dim, (xd,), True
+    for n in FULL_SIZES:             # values only; the same values from offsets 0, 1, 3 of a buffer
+        seed += 1
+        done = set()
+        for x, kinds in RR.make_hard_batches((n,), None, dn, 100 * seed):
+            if kinds[0] == 'tie_pair' and 'tie_pair' in done:
+                continue             # without indices the four placements of the pair are one case
+            done.add(kinds[0])
+            tensors = []
+            for off in (0, 1, 3):
+                buf = np.zeros(n + 3, x.dtype)
+                buf[off:off + n] = x
+                tensors.append(t(buf, dev)[off:off + n])
+            yield f'full n={n}', x, kinds, None, tuple(tensors), False
+    seed += 1
+    for x, kinds in RR.make_hard_batches(MID_SHAPE, MID_DIMS, dn, 100 * seed):
+        yield f'{MID_SHAPE} dim={MID_DIMS}', x, kinds, MID_DIMS, (t(x, dev),), True
+
+
+def _judge_sums_and_picks(xd, tr, dim, dn, tag, want_idx):
+    """every function of one input, a verdict for every output slice; returns the worst sum error / bound per
+    function (float64 input: dtype=float64 is the input dtype)"""
+    import _reduce_ref as RR
+    r = R()
+    worst = {}
+
+    def host(v):
+        return v.cpu().numpy()
+
+    for out_dtype in ((None, torch.float64) if dn == 'f32' else (None,)):
+        odt, sfx = (np.float64, '64') if out_dtype is not None else (RR.DT[dn], '')
+        worst['sum' + sfx] = tr.judge_sum(host(r.sum(xd, dim, dtype=out_dtype)), False, odt, tag)
+        worst['nansum' + sfx] = tr.judge_sum(host(r.nansum(xd, dim, dtype=out_dtype)), True, odt, tag)
+    for which, omitnan, fn in (('max', False, r.max), ('min', False, r.min), ('max', True, r.nanmax), ('min', True, r.nanmin)):
+        plain = host(fn(xd, dim))
+        tr.judge_value(plain, which, omitnan, tag)
+        if want_idx:
+            val, idx = fn(xd, dim, return_indices=True)
+            tr.judge_pair(host(val), host(idx), plain, which, omitnan, tag)
+    return worst
+
+
+def test_staged_nansum_propagates_inf_minus_inf(dev):
+    """non-adjacent dims: +inf and -inf give NaN whether they meet in one partial sum of the first stage or only in
+    the second; NaNs of the data are omitted, also where they fill a whole partial sum"""
+    inf, nan = np.inf, np.nan
+    x = np.arange(2 * 3 * 4 * 4, dtype=np.float32).reshape(2, 3, 4, 4)        # reduced over (0, 2): kept (3, 4)
+    x[0, 0, 1, 0], x[0, 0, 3, 0] = inf, -inf          # output (0, 0): both in the partial sum of outer index 0
+    x[0, 1, 0, 1], x[1, 1, 2, 1] = inf, -inf          # output (1, 1): one in each partial sum
+    x[1, 2, :, 2] = nan                               # output (2, 2): one partial sum all NaN
+    x[0, 2, 1, 3], x[1, 2, 1, 3] = inf, nan           # output (2, 3): +inf alone, next to a NaN
+    got = R().nansum(t(x, dev), dim=(0, 2)).cpu().numpy()
+    with np.errstate(invalid='ignore'):
+        ref = np.where(np.isnan(x), 0, x).astype(np.float64).sum((0, 2))
+    assert np.isnan(ref[0, 0]) and np.isnan(ref[1, 1]) and np.isfinite(ref[2, 2]) and ref[2, 3] == inf
+    assert np.array_equal(got, ref.astype(np.float32), equal_nan=True), (got, ref)
+    assert np.isnan(R().sum(t(x, dev), dim=(0, 2)).cpu().numpy()[[0, 1, 2, 2], [0, 1, 2, 3]]).all()
+
+
+@pytest.mark.parametrize('dn', ['f32', 'f64'])
+def test_sums_and_picks_on_hard_slices(dev, dn):
+    """sum / nansum (in the input dtype and with dtype=float64), max / min / nanmax / nanmin without and with
+    indices, on every route of the moments test -- aligned and one element off a 16-byte line, staged, permuted
+    view, full reduction from offsets 0, 1, 3 -- and over two adjacent middle dims.  Every slice of every kind of
+    `_reduce_ref.hard_entries` is judged on every route: sums to eps_out |S| + n u A + one subnormal around the
+    fsum truth (for float64 input the n u A term is far above what a correct kernel does: there is no wider
+    accumulator to compare with), extrema by `==`, indices as the first position after NaN replacement / the
+    first NaN, which is what the reference's `_reduce_index` returns (it replaces NaN by -inf / +inf and calls
+    torch.max / torch.min: index 0 on `nan_then_ninf` and `all_nan`).
+
+    On the parent of the commit that added this test `nansum` failed on the staged routes, on `both_inf` slices
+    whose +inf and -inf lie in one partial sum of the first stage (a finite result instead of NaN, float32 over
+    dims (0, 2, 3, 4) and float64 over dims (1, 3)): the second stage, itself a nansum, omitted that NaN.
+    test_staged_nansum_propagates_inf_minus_inf puts the two there on purpose.  Every route before the staged
+    ones passed; with the fix all pass (profiles/reduce_accuracy.md)."""
+    import _reduce_ref as RR
+    ratios, met, judged = {}, {}, 0
+    for route, x, kinds, dim, tensors, want_idx in _hard_inputs(dn, dev):
+        tr = RR.SumPickTruth(x, dim)
+        met.setdefault(route, set()).update(kinds)
+        per = ratios.setdefault(route, {})
+        for xd in tensors:
+            for fn, ratio in _judge_sums_and_picks(xd, tr, dim, dn, route, want_idx).items():
+                per[fn] = max(per.get(fn, 0.0), ratio)
+            judged += len(kinds)
+    print(f'HARD {dn}: {judged} slices judged on {len(ratios)} routes; worst sum error/bound ' +
+          '; '.join(f'{k}: {max(v.values()):.3g}' for k, v in ratios.items()))
+    for route, per in ratios.items():
+        print(f'HARD {dn} | `{route}` | ' + ' | '.join(f'{per[fn]:.2g}' for fn in sorted(per)) + f' | ({", ".join(sorted(per))})')
+    every = set(RR.hard_kinds(dn)) | {'normal'}
+    assert all(m == every for m in met.values()), {k: every - m for k, m in met.items() if m != every}
+    assert len(ratios) == len(MOMENT_ROUTES) + len(STAGED_DIMS) + len(PERM_DIMS) + len(FULL_SIZES) + 1
+    assert judged > 19_000 and max(max(v.values()) for v in ratios.values()) <= 1.0
