@@ -305,6 +305,34 @@ int nfm_sym_chol_max_order(int dtype, int op_class);
 int nfm_sym_chol_host(int dtype, int M, int op, int64_t n, const void *mat, const void *vec, const void *gout,
                       void *out);
 
+/* EXTENSION: the gradient of the factor itself (the backward pass of NFM_CHOL_FACTOR and of the four apply ops), one
+ * record per lane: the factor is recomputed (or adopted) in registers and pulled back by two triangular sweeps.
+ * nfm_sym_chol_grad: op =
+ *   NFM_CHOL_FACTOR         gout = the cotangent of the factor: M (M + 1) / 2 values per record, one per stored entry
+ *                           L_ij (i >= j), each counted once; vec is not read (NULL); gpacked = M (M + 1) / 2 values:
+ *                           S = L^-T (P + P^T) L^-1 / 2, P = the lower triangle of L^T gout with a halved diagonal, in
+ *                           the compact convention of nfm_sym_chol_backward (S_ii, 2 S_ij).  Or'ed with
+ *                           NFM_CHOL_FACTORED, `mat` is the factor already computed (the saved result of the forward).
+ *   NFM_CHOL_APPLY_*        gout = the cotangent of the applied vector (M values); gpacked = M (M + 1) / 2 + M values,
+ *                           the gradient with respect to mat, then the one with respect to vec (gvec).  With y the
+ *                           forward result: _L gvec = L^T gout, G = tril(gout vec^T); _LT gvec = L gout, G = tril(vec
+ *                           gout^T); _LINV gvec = L^-T gout, G = -tril(gvec y^T); _LTINV gvec = L^-1 gout, G = -tril(y
+ *                           gvec^T).  G is pulled back to S as above; or'ed with NFM_CHOL_FACTORED, `mat` is a factor
+ *                           and the first part of gpacked is G itself, plain: one value per stored entry.
+ * The scalar op codes are NFM_EINVAL here (their gradient is nfm_sym_chol_backward).  Bad records as nfm_sym_chol (with
+ * NFM_CHOL_FACTORED: a diagonal that is not > 0), and a cotangent entry that is not finite: NaN in every value.
+ * M in 1..nfm_sym_chol_grad_max_order(dtype, class), class = NFM_CHOL_CLASS_FACTOR or NFM_CHOL_CLASS_APPLY (0 for any
+ * other class or dtype).  Status precedence: that of nfm_sym_chol. */
+int nfm_sym_chol_grad(int dtype, int M, int op, int64_t n_outer, int64_t n_inner, const nfm_operand *mat,
+                      const nfm_operand *vec, const nfm_operand *gout, const nfm_operand *gpacked, void *stream);
+int nfm_sym_chol_grad_max_order(int dtype, int op_class);
+/* CPU: the same record routines on n contiguous host records of order M <= 8 (NFM_ESIZE beyond): mat (n M (M + 1) / 2
+ * values), vec (n M values, or NULL for NFM_CHOL_FACTOR), gout and out as gout and gpacked above.  NFM_EDTYPE;
+ * NFM_EINVAL for n < 0, an op that is neither the factor nor an apply, or a null mat, gout, out or needed vec with
+ * n > 0. */
+int nfm_sym_chol_grad_host(int dtype, int M, int op, int64_t n, const void *mat, const void *vec, const void *gout,
+                           void *out);
+
 /* -------------------------------------------------------------- batched ---- */
 
 #define NFM_FLAG_TS_PERTURB 1 /* add (max|A| - min|A|) * 1e-12 to det for N in {2,3}:

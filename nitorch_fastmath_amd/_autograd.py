@@ -491,6 +491,65 @@ def _to_input(g, like):
     return g.sum_to_size(like.shape).to(like.dtype)
 
 
+class SymCholFactorFn(torch.autograd.Function):
+    """The Cholesky factor of compact symmetric matrices (sym.sym_chol).  Nothing but `mat` is saved: one backward
+    kernel factors again in registers and pulls the cotangent of the factor back to the matrix.  Differentiable twice:
+    called with grad mode enabled (`create_graph=True`), backward differentiates the torch composition instead."""
+
+    @staticmethod
+    def forward(ctx, mat, dtype):
+        from . import sym as S
+        with torch.no_grad():
+            res = S._chol_forward(S._lib.CHOL_FACTOR, S._lib.CHOL_CLASS_FACTOR, mat, None, dtype, None, None)
+        ctx.save_for_backward(mat)
+        ctx.cfg = (dtype, res.dtype)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import sym as S
+        (mat,) = ctx.saved_tensors
+        dtype, cdt = ctx.cfg
+        if torch.is_grad_enabled():
+            (gmat,) = torch.autograd.grad(S._chol_route('chol', dtype, mat), mat, g, create_graph=True)
+            return gmat, None
+        return _to_input(S._chol_grad(S._lib.CHOL_FACTOR, mat, None, g, cdt), mat), None
+
+
+class SymCholApplyFn(torch.autograd.Function):
+    """L v, L^T v, L^-1 v, L^-T v of compact symmetric matrices or of their factors (sym.sym_chol_apply).  Nothing but
+    the two inputs is saved: one backward kernel recomputes the factor and the result and writes the packed gradient
+    [K | M], returned as two views reduced to the inputs' own (possibly broadcast) shapes.  Differentiable twice as
+    SymCholFactorFn."""
+
+    @staticmethod
+    def forward(ctx, mat, vec, op, factored, dtype):
+        from . import sym as S
+        code = S._lib.CHOL_APPLY[op] | (S._lib.CHOL_FACTORED if factored else 0)
+        with torch.no_grad():
+            res = S._chol_forward(code, S._lib.CHOL_CLASS_APPLY, mat, vec, dtype, None, None)
+        ctx.save_for_backward(mat, vec)
+        ctx.cfg = (op, factored, code, dtype, res.dtype)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import sym as S
+        mat, vec = ctx.saved_tensors
+        op, factored, code, dtype, cdt = ctx.cfg
+        need = ctx.needs_input_grad[:2]
+        if torch.is_grad_enabled():
+            wrt = [t for t, n in zip((mat, vec), need) if n]
+            res = S._chol_route('chol_apply', dtype, mat, vec, op=op, factored=factored)
+            grads = list(torch.autograd.grad(res, wrt, g, create_graph=True))
+            return (grads.pop(0) if need[0] else None), (grads.pop(0) if need[1] else None), None, None, None
+        packed = S._chol_grad(code, mat, vec, g, cdt)
+        K = mat.shape[-1]
+        gmat = _to_input(packed[..., :K], mat) if need[0] else None
+        gvec = _to_input(packed[..., K:], vec) if need[1] else None
+        return gmat, gvec, None, None, None
+
+
 class SymPencilFunmFn(torch.autograd.Function):
     """A^1/2 f(A^-1/2 B A^-1/2) A^1/2 of compact matrices (sym.sym_pencil_funm).  Only the two inputs are saved: the
     backward kernel recomputes both decompositions.  With respect to `mat`: the backward kernel.  With respect to

@@ -103,6 +103,10 @@ SIGNATURES = {
     'nfm_sym_chol_backward': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'nfm_sym_chol_max_order': [_i, _i],
     'nfm_sym_chol_host': [_i, _i, _i, _i64, _vp, _vp, _vp, _vp],
+    # (the same; tests/test_cholgrad_host.py makes the canonical bad calls)
+    'nfm_sym_chol_grad': [_i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    'nfm_sym_chol_grad_max_order': [_i, _i],
+    'nfm_sym_chol_grad_host': [_i, _i, _i, _i64, _vp, _vp, _vp, _vp],
     'nfm_batch_inv': [_i, _i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_det': [_i, _i, _i64, _i64, _op, _op, _vp],
     'nfm_batch_matvec': [_i, _i, _i, _i64, _i64, _op, _op, _op, _vp],

@@ -1,6 +1,7 @@
 """Cholesky functions of compact symmetric matrices in plain torch: the route of `sym.sym_chol`, `sym_chol_apply`,
-`sym_logdet`, `sym_mahalanobis` and `sym_gauss_logpdf` for the orders that have no kernel (`nfm_sym_chol_max_order`),
-and of `sym_chol` / `sym_chol_apply` whenever a gradient is asked for (the factor itself has no backward kernel).
+`sym_logdet`, `sym_mahalanobis` and `sym_gauss_logpdf` for the orders that have no kernel (`nfm_sym_chol_max_order`,
+`nfm_sym_chol_grad_max_order`), and what the backward pass of `sym_chol` / `sym_chol_apply` differentiates when a second
+derivative is asked for (`create_graph=True`: the backward kernels are differentiable once).
 Private and device-agnostic: it runs on CPU tensors too when called directly (the host tests do).
 
 compact -> full -> `torch.linalg.cholesky_ex` -> products and triangular solves, differentiated by torch.  The bad-record

@@ -725,7 +725,8 @@ def _chol_shapes(mat, vec):
 
 
 def _chol_route(name, dtype, mat, vec=None, **kw):
-    """the torch composition (`_symchol.py`) on the device: orders without a kernel, and the differentiable factor"""
+    """the torch composition (`_symchol.py`) on the device: orders without a kernel, forward or backward, and the second
+    derivatives of the factor"""
     from . import _symchol
     _, _, ts = prepare(dtype, mat, vec, grad_ok=True)
     return getattr(_symchol, name)(*[t for t in ts if t is not None], **kw)
@@ -792,6 +793,35 @@ def _chol_scalar(op, mat, vec, dtype, out):
     return _chol_forward(op, _lib.CHOL_CLASS_SCALAR, mat, vec, dtype, out, route)
 
 
+def _chol_grad_cap(dtype, cls):
+    """largest order with a backward kernel for the factor (`CHOL_CLASS_FACTOR`) or an apply op (`CHOL_CLASS_APPLY`)"""
+    return max_order('nfm_sym_chol_grad_max_order', dtype, cls)
+
+
+def _chol_grad_fits(dtype, mat, vec, cls):
+    """the order has a forward and a backward kernel for the class in the computing dtype"""
+    M, _ = _chol_shapes(mat, vec)
+    _, cdt, _ = prepare(dtype, mat, vec, grad_ok=True)
+    return M <= min(_chol_cap(cdt, cls), _chol_grad_cap(cdt, cls))
+
+
+def _chol_grad(op, mat, vec, gout, dtype):
+    """one launch of `nfm_sym_chol_grad`: the packed gradient `(..., K)` of the factor, or `(..., K + M)` of an apply op,
+    for the cotangent `gout` (of the broadcast batch shape)"""
+    dev, dtype, (mat, vec, gout) = prepare(dtype, mat, vec, gout)
+    M, K = _chol_shapes(mat, vec)
+    batch = tuple(gout.shape[:-1])
+    packed = torch.empty(batch + (K + (0 if vec is None else M),), dtype=dtype, device=dev)
+    gout = gout.contiguous()
+    if vec is None:
+        b = Batch(batch, [expand_batch(batch, mat, 1), gout, packed], [1, 1, 1])
+        launch(_lib.lib().nfm_sym_chol_grad, dev, dtype, (M, op), b, slots=(0, None, 1, 2))
+    else:
+        b = Batch(batch, [expand_batch(batch, mat, 1), expand_batch(batch, vec, 1), gout, packed], [1, 1, 1, 1])
+        launch(_lib.lib().nfm_sym_chol_grad, dev, dtype, (M, op), b)
+    return packed
+
+
 def sym_chol(mat, dtype=None, out=None):
     r"""EXTENSION (not in the reference): the Cholesky factor of compact symmetric positive definite matrices.
 
@@ -804,14 +834,24 @@ def sym_chol(mat, dtype=None, out=None):
     result and of its gradient; its neighbours are untouched.  No exception, no host synchronisation: a call can be
     captured in a graph.  Nothing is scaled: `sym_chol(s^2 A) == s * sym_chol(A)` bit for bit for a power of two `s`.
 
-    dtype, out : as `sym_det`; `out=mat` (in place) is allowed.  With `requires_grad` the factor is computed by a torch
-    composition on the device (`torch.linalg.cholesky_ex`): there is no backward kernel for the factor itself.  Orders
-    above the compiled cap (8) take the same composition.
+    dtype, out : as `sym_det`; `out=mat` (in place) is allowed.
+
+    Differentiable: with `requires_grad` the same forward kernel runs (the same bits) and one backward kernel pulls the
+    cotangent `G` of the factor (compact, one value per stored `L_ij`) back to
+    `S = L^-T (P + P^T) L^-1 / 2`, `P` = the lower triangle of `L^T G` with a halved diagonal, returned as `S_ii`,
+    `2 S_ij`.  Nothing is saved but `mat`: the backward kernel factors again in registers, which costs no memory traffic
+    (the C entry also takes the factor itself, `NFM_CHOL_FACTORED`).  A record with a cotangent entry that is not finite
+    is NaN in its gradient.  A second derivative
+    (`create_graph=True`) differentiates the torch composition on the device (`torch.linalg.cholesky_ex`), which is
+    also what orders above the compiled cap (8) run, forward and backward.
     """
     _chol_shapes(mat, None)
     if needs_grad(mat):
         _grad_guard(out)
-        return _chol_route('chol', dtype, mat)
+        if not _chol_grad_fits(dtype, mat, None, _lib.CHOL_CLASS_FACTOR):
+            return _chol_route('chol', dtype, mat)
+        from ._autograd import SymCholFactorFn
+        return SymCholFactorFn.apply(torch.as_tensor(mat), dtype)
     return _chol_forward(_lib.CHOL_FACTOR, _lib.CHOL_CLASS_FACTOR, mat, None, dtype, out, _CHOL_ROUTE[_lib.CHOL_FACTOR])
 
 
@@ -821,15 +861,26 @@ def sym_chol_apply(mat, vec, op, factored=False, dtype=None, out=None):
     op : 'L' for `L v` (colouring a white sample), 'LT' for `L^T v`, 'Linv' for `L^-1 v` (whitening), 'LTinv' for
         `L^-T v`.
     factored : `mat` already is the result of `sym_chol`, so one factorisation serves many vectors (same bits).
-    Either operand may be broadcast, as in `sym_matvec`.  Bad records, `dtype`, `out` and gradients as `sym_chol`.
+    Either operand may be broadcast, as in `sym_matvec`.  Bad records, `dtype`, `out` as `sym_chol`.
+
+    Differentiable in `mat` and `vec`: the forward kernel (the same bits as without `requires_grad`), and one backward
+    kernel that saves nothing but the two inputs and recomputes the factor and the result.  With the cotangent `g` and
+    the result `y`: 'L' `g_v = L^T g`, `G = tril(g v^T)`; 'LT' `g_v = L g`, `G = tril(v g^T)`; 'Linv' `g_v = L^-T g`,
+    `G = -tril(g_v y^T)`; 'LTinv' `g_v = L^-1 g`, `G = -tril(y g_v^T)`.  With `factored` the gradient of `mat` is `G`
+    itself (one value per stored entry of the factor); without, `G` is pulled back to `A` in the same lane as in
+    `sym_chol`.  The gradient of a broadcast operand is summed to its shape.  Second derivatives and orders above 8 as
+    `sym_chol`.
     """
     if op not in _lib.CHOL_APPLY:
         raise ValueError(f"op must be one of {sorted(_lib.CHOL_APPLY)}, got {op!r}")
     _chol_shapes(mat, vec)
+    code = _lib.CHOL_APPLY[op] | (_lib.CHOL_FACTORED if factored else 0)
     if needs_grad(mat, vec):
         _grad_guard(out)
-        return _chol_route('chol_apply', dtype, mat, vec, op=op, factored=bool(factored))
-    code = _lib.CHOL_APPLY[op] | (_lib.CHOL_FACTORED if factored else 0)
+        if not _chol_grad_fits(dtype, mat, vec, _lib.CHOL_CLASS_APPLY):
+            return _chol_route('chol_apply', dtype, mat, vec, op=op, factored=bool(factored))
+        from ._autograd import SymCholApplyFn
+        return SymCholApplyFn.apply(torch.as_tensor(mat), torch.as_tensor(vec), op, bool(factored), dtype)
     return _chol_forward(code, _lib.CHOL_CLASS_APPLY, mat, vec, dtype, out,
                          ('chol_apply', {'op': op, 'factored': bool(factored)}))
 
